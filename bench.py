@@ -13,6 +13,13 @@ value = gates x steps / wall time (every gate is applied once forward and once i
 reverse sweep); inputs are resident in HBM before the timed region (gate matrices are 16-256 B
 host arrays passed per call, as in the reference API).
 
+A plain run (bench.py --gpus 1 --steps N --warmup W) does what the headline needs and no more:
+set up, warm up, time the N steps (with the per-launch HIP events of the roofline block), print
+the line.  --full adds what takes runs of its own: the single-gate kernel sweep, the dense-gate
+and C3 VQSE samples, the unfused C ABI step and the CPU baseline (minutes; their blocks of the
+line are null without it).  --dump-outputs DIR writes the last timed step's densities and
+gradients as DIR/densities.npy and DIR/gradients.npy (dump_outputs).
+
 Multi-GPU (python -m torch.distributed.run ... bench.py --gpus N, torch only as the launcher):
 strong scaling — the SAME
 n-qubit state is sharded over the N GPUs by its high qubits; gates on a global
@@ -95,6 +102,14 @@ def parse(argv=None):
     ap.add_argument("--jit-wait-max-s", type=float, default=1500.0,
                     help="longest wait for background-compiled specialized kernels after warm-up")
     ap.add_argument("--micro", action="store_true", help="per-kernel bandwidth sweep")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the "
+                         "auxiliary samples (single-gate kernel sweep, dense k-qubit gates, C3 VQSE "
+                         "in both precisions, the unfused C ABI step) and the CPU baseline; "
+                         "--no-gate-sample / --no-cpu-baseline drop either part")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to its caller (the densities of "
+                         "forward, the gate gradients of backward) as DIR/<name>.npy")
     args = ap.parse_args(argv)
     wl = WORKLOADS[args.workload]
     args.qubits = wl["qubits"] if args.qubits is None else args.qubits
@@ -143,6 +158,21 @@ def build_circuit(q, n, layers, seed, precision, comm=None, local_shards=None, d
 def sigma_z_cotangents(ndens, dt):
     # d/d rho of Re tr(rho sigma_z) is sigma_z^T; the qdc wiring conjugates it (circuit.py:193)
     return [np.ascontiguousarray(np.diag([1.0, -1.0]).astype(dt)) for _ in range(ndens)]
+
+
+def dump_outputs(path, dens, grads):
+    """The last timed step's results as its caller received them: densities.npy (forward's
+    density matrices, in instruction order) and gradients.npy (backward's gate gradients, in
+    gate order).  The matrices of a list differ in size (2x2, 4x4, diagonals), so each file is
+    their row-major elements one after the other, shape (elements, 2) = (re, im), in the
+    state's real type (float32 / float64).  The inputs are seeded, so two builds run with the
+    same arguments can be compared file for file.  About 1 MB at most (C5: 10 000 gates)."""
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, arrs in (("densities", dens), ("gradients", grads)):
+        flat = np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in arrs])
+        real = np.float64 if flat.dtype == np.complex128 else np.float32
+        np.save(out / f"{name}.npy", np.stack([flat.real, flat.imag], axis=1).astype(real))
 
 
 def dist_setup(args):
@@ -768,6 +798,8 @@ def main():
     if not os.environ.get("QDC_BENCH_ABLATION"):
         assert all(np.isfinite(g).all() for g in grads)
         assert all(abs(np.trace(d) - 1) < 1e-3 for d in dens)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dens, grads)
 
     # the fused path against the per-gate roofline: every gate costs 2S forward and 4S in the
     # reverse sweep (SURVEY.md §8 d) if applied one HBM pass at a time
@@ -801,8 +833,9 @@ def main():
 
     gate_kernels = dense_kernels = vqse = vqse32 = abi = None
     # (the auxiliary samples and the CPU baseline belong to the one-GPU headline: a sharded run —
-    # any number of processes, GPUs or local shards — reports its own step and exchange only)
-    if rank == 0 and shards == 1 and not args.no_gate_sample and args.workload == "c2":
+    # any number of processes, GPUs or local shards — reports its own step and exchange only;
+    # both take runs of their own, minutes of them, so a plain run leaves them out: --full)
+    if args.full and rank == 0 and shards == 1 and not args.no_gate_sample and args.workload == "c2":
         # auxiliary samples: a failure there is reported in the line, never loses the headline
         def aux(fn, *a):
             try:
@@ -817,7 +850,7 @@ def main():
             abi = aux(abi_unfused_sample, args, n)
 
     cpu = None
-    if rank == 0 and shards == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and shards == 1 and not args.no_cpu_baseline:
         try:
             with heartbeat("CPU baseline (the reference's algorithm on the host cores)"):
                 cpu = cpu_baseline(args, args.cpu_qubits or n)

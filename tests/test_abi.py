@@ -104,8 +104,8 @@ def test_flatten_helpers():
 
 
 # ------------------------------------------------------------------------------------------
-# Rust views of the C ABI: the reference's primitives_bind.rs against primitives.h, and the
-# circuit_bind.rs block of INTEGRATION.md §3a against circuit.h (names, arity, every type)
+# Other views of the C ABI: the circuit_bind.rs block of INTEGRATION.md §3a against circuit.h,
+# and the package's ctypes table against primitives.h (names, arity, every type)
 # ------------------------------------------------------------------------------------------
 C_TO_RUST = {
     "void": None, "size_t": "usize", "int": "c_int", "unsigned": "c_uint", "double": "f64",
@@ -186,14 +186,25 @@ def test_integration_rust_block_matches_circuit_header():
     _compare(cdecl, rdecl, cdecl)
 
 
-REF_BIND = Path("/root/reference/src/primitives_bind.rs")
+C_TO_CTYPES = {
+    "void": None, "const char*": ctypes.c_char_p, "size_t": ctypes.c_size_t,
+    "qdc_complex*": ctypes.c_void_p, "const qdc_complex*": ctypes.c_void_p,
+    "qdc_complex**": ctypes.POINTER(ctypes.c_void_p),
+}
 
 
-@pytest.mark.skipif(not REF_BIND.exists(), reason="reference tree not present")
-def test_primitives_header_matches_reference_bindings():
-    """include/qdc/primitives.h declares the 18 functions of src/primitives_bind.rs:15-119 with
-    the types the reference's Rust binds them with (so its crate links libqdc unchanged)."""
+def test_primitives_header_matches_binding_table():
+    """include/qdc/primitives.h declares exactly the 18 functions of the reference's ABI
+    (src/primitives_bind.rs:15-119), each with the return and parameter types the package's own
+    binding table gives it (_native._proto): the two statements of that ABI the repository
+    keeps, so neither drifts alone (name, arity, every type)."""
+    from quantum_differentiable_circuit import _native
     cdecl = c_declarations(ROOT / "include" / "qdc" / "primitives.h")
-    rdecl = rust_declarations(REF_BIND.read_text().replace("pub(super) ", ""))
-    assert len(rdecl) == 18 and set(rdecl) <= set(cdecl), set(rdecl) - set(cdecl)
-    _compare(cdecl, rdecl, rdecl)
+    assert len(_native.PRIMITIVES) == 18 and set(cdecl) == set(_native.PRIMITIVES), \
+        set(cdecl) ^ set(_native.PRIMITIVES)
+    lib = _native.load("f32")
+    for name in _native.PRIMITIVES:
+        cret, cparams = cdecl[name]
+        fn = getattr(lib, name)
+        assert C_TO_CTYPES[cret] == fn.restype, (name, cret, fn.restype)
+        assert [C_TO_CTYPES[t] for t in cparams] == list(fn.argtypes), (name, cparams, fn.argtypes)

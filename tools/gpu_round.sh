@@ -20,7 +20,7 @@ done
 step pmc-summary
 python3 tools/pmc_summary.py "$OUT" "$OUT/summary" > "$OUT/pmc_summary.log" 2>&1 || exit $?
 step bench
-timeout -k 10 900 python bench.py --pmc "$OUT/pmc_traffic.json" > "$OUT/bench.log" 2>&1 || exit $?
+timeout -k 10 900 python bench.py --full --pmc "$OUT/pmc_traffic.json" > "$OUT/bench.log" 2>&1 || exit $?
 tail -c 600 "$OUT/bench.log"; echo
 step rocprof-kernel-trace
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace \

@@ -7,6 +7,6 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 OUT=gpurun_out/r5t
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 900 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+timeout -k 10 900 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 tail -c 600 "$OUT/bench.json"; echo
 TAG=r5t/shard bash tools/shard_rehearsal.sh

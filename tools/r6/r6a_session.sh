@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 timeout -k 10 900 python -u -m pytest tests/test_gpu_c5_shards.py tests/test_gpu_vqse.py tests/test_gpu_mirror.py \
   -x -v -s --timeout 600 --timeout-method thread > "$OUT/tests.log" 2>&1
 rc=$?; grep -E "passed|failed|error" "$OUT/tests.log" | tail -3; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python -u bench.py --steps 5 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python -u bench.py --full --steps 5 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; tail -c 300 "$OUT/bench.json"; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 400 python -u bench.py --steps 3 --warmup 1 --local-shards 8 > "$OUT/bench_shards8.json" 2> "$OUT/bench_shards8.err"
 rc=$?; tail -c 600 "$OUT/bench_shards8.json"; [ $rc -eq 0 ] || exit $rc

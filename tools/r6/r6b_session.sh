@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 timeout -k 10 1000 python -u -m pytest tests/test_gpu_fusion.py tests -m gpu -x -v --timeout 400 --timeout-method thread \
   --deselect tests/test_gpu_drift.py::test_c5_full_size_10k_gates > "$OUT/tests.log" 2>&1
 rc=$?; grep -E "passed|failed|error" "$OUT/tests.log" | tail -3; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python -u bench.py --steps 10 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python -u bench.py --full --steps 10 --warmup 2 > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; tail -c 400 "$OUT/bench.json"; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace \
   -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gate-sample > "$OUT/trace.log" 2>&1

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 OUT=gpurun_out/r6g
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?; tail -c 300 "$OUT/bench.json"; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o trace \
   -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-gate-sample > "$OUT/trace.log" 2>&1
@@ -21,5 +21,5 @@ python3 tools/pmc_summary.py "$OUT" "$OUT/summary" > "$OUT/pmc_summary.log" 2>&1
 tail -9 "$OUT/pmc_summary.log"
 timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --local-shards 8 > "$OUT/bench_shards8.json" 2> "$OUT/bench_shards8.err"
 rc=$?; tail -c 300 "$OUT/bench_shards8.json"; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python -u bench.py --workload c4 --steps 2 --warmup 1 --no-gate-sample > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
+timeout -k 10 400 python -u bench.py --full --workload c4 --steps 2 --warmup 1 --no-gate-sample > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"
 rc=$?; tail -c 300 "$OUT/bench_c4.json"; exit $rc
