@@ -13,6 +13,7 @@
 #include "qdc/dense.h"
 #include "qdc_device.hpp"
 #include "qdc_qk.hpp"
+#include "qdc_qkgrad.hpp"
 
 namespace qdc {
 
@@ -301,12 +302,9 @@ __attribute__((visibility("default"))) void copy(const qdc_complex* src, qdc_com
 
 // ---- extensions beyond the reference's 18 entry points (include/qdc/dense.h) ----------------
 
-__attribute__((visibility("default"))) const char* qdc_qkgate(qdc_complex* state,
-                                                              const qdc_complex* gate,
-                                                              const size_t* pos, size_t k,
-                                                              size_t n) {
-  QDC_ABI_BEGIN
-  QDC_TRY(qdc::check_n(n));
+}  // extern "C"
+
+static const char* check_qk(const size_t* pos, size_t k, size_t n) {
   if (k < 1 || k > (size_t)qdc::QK_MAX)
     return qdc::fail("k = %zu qubits is out of the supported range (1..%d).", k, qdc::QK_MAX);
   if (k > n) return qdc::fail("k = %zu exceeds qubits_number %zu.", k, n);
@@ -315,9 +313,60 @@ __attribute__((visibility("default"))) const char* qdc_qkgate(qdc_complex* state
     for (size_t c = 0; c < b; ++c)
       if (pos[c] == pos[b]) return qdc::fail("positions must be different.");
   }
+  return nullptr;
+}
+
+extern "C" {
+
+__attribute__((visibility("default"))) const char* qdc_qkgate(qdc_complex* state,
+                                                              const qdc_complex* gate,
+                                                              const size_t* pos, size_t k,
+                                                              size_t n) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  QDC_TRY(check_qk(pos, k, n));
   static qdc::QkRing rings[qdc::ABI_MAX_DEVICES];  // guarded by the ABI mutex
   return qdc::apply_qk(ctx, reinterpret_cast<qdc::cx*>(state), gate, pos, (uint32_t)k,
                        (uint32_t)n, rings[ctx.device]);
+}
+
+__attribute__((visibility("default"))) const char* qdc_qkgrad(const qdc_complex* fwd,
+                                                              const qdc_complex* bwd,
+                                                              qdc_complex* grad,
+                                                              const size_t* pos, size_t k,
+                                                              size_t n) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  QDC_TRY(check_qk(pos, k, n));
+  const qdc::cx* f = reinterpret_cast<const qdc::cx*>(fwd);
+  const qdc::cx* b = reinterpret_cast<const qdc::cx*>(bwd);
+  if (k <= 2) {  // q1grad / q2grad(pos[0], pos[1]), bit for bit
+    const uint32_t p2 = (uint32_t)pos[0], p1 = (uint32_t)pos[k - 1];
+    QDC_TRY(k == 1 ? qdc::grad_dense<2>(ctx, f, b, p2, p1, (uint32_t)n, ctx.results, 0, 0)
+                   : qdc::grad_dense<4>(ctx, f, b, p2, p1, (uint32_t)n, ctx.results, 0, 0));
+    return qdc::abi_finish_reduction(ctx, grad, k == 1 ? 4 : 16);
+  }
+  static qdc::QkgScratch scratch[qdc::ABI_MAX_DEVICES];  // guarded by the ABI mutex
+  return qdc::reduce_qk(ctx, f, b, grad, pos, (uint32_t)k, (uint32_t)n, scratch[ctx.device]);
+}
+
+__attribute__((visibility("default"))) const char* qdc_qkdensity(const qdc_complex* state,
+                                                                 qdc_complex* density,
+                                                                 const size_t* pos, size_t k,
+                                                                 size_t n) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  QDC_TRY(check_qk(pos, k, n));
+  const qdc::cx* s = reinterpret_cast<const qdc::cx*>(state);
+  if (k <= 2) {  // get_q1density / get_q2density(pos[0], pos[1]), bit for bit
+    const uint32_t p2 = (uint32_t)pos[0], p1 = (uint32_t)pos[k - 1];
+    QDC_TRY(k == 1 ? qdc::density<2>(ctx, s, p2, p1, (uint32_t)n, ctx.results, 0, 0)
+                   : qdc::density<4>(ctx, s, p2, p1, (uint32_t)n, ctx.results, 0, 0));
+    return qdc::abi_finish_reduction(ctx, density, k == 1 ? 4 : 16);
+  }
+  static qdc::QkgScratch scratch[qdc::ABI_MAX_DEVICES];  // guarded by the ABI mutex
+  return qdc::reduce_qk(ctx, s, nullptr, density, pos, (uint32_t)k, (uint32_t)n,
+                        scratch[ctx.device]);
 }
 
 __attribute__((visibility("default"))) const char* qdc_abi_sync(void) {

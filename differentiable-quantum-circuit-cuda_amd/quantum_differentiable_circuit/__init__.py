@@ -25,7 +25,8 @@ from ._native import (PanicException, KernelStat, PlanOp, check, default_precisi
                       ptr, PRECISIONS)
 
 __all__ = ["Circuit", "Circuit32", "Circuit64", "QuantizedTensor", "PanicException",
-           "get_q1_grad", "get_q2_grad", "get_q2_grad_diag", "data_transfer", "circuit_class",
+           "get_q1_grad", "get_q2_grad", "get_q2_grad_diag", "get_qk_grad", "data_transfer",
+           "circuit_class",
            "plan", "unpermute", "get_hadamard", "get_cnot"]
 
 # enum Instruction order (src/circuit.rs:53-68) == enum qdc_kind (include/qdc/circuit.h)
@@ -573,6 +574,18 @@ def spec_fingerprint(csrc_dir, compiler, defines=None, precision="f32"):
 # ---------------------------------------------------------------------------------------
 # QuantizedTensor (src/quantized_tensor.rs:54-238) over the 18-function C ABI
 # ---------------------------------------------------------------------------------------
+def _qk_positions(pos, qubits_number):
+    """The checks of the dense k-qubit entry points (qdc_qkgate's), then the size_t array."""
+    k = len(pos)
+    if not 1 <= k <= 5:
+        raise PanicException("k must be in 1..5.")
+    if len(set(pos)) != k:
+        raise PanicException("positions must be different.")
+    if max(pos) >= qubits_number:
+        raise PanicException("pos is out of the bound.")
+    return (C.c_size_t * k)(*pos)
+
+
 class QuantizedTensor:
     """A device state of 2^n amplitudes owned by this object (RAII like the Rust struct)."""
 
@@ -686,12 +699,27 @@ class QuantizedTensor:
         if not 1 <= k <= 5:
             raise PanicException("k must be in 1..5.")
         g = self._gate(gate, 1 << (2 * k))
-        if len(set(pos)) != k:
-            raise PanicException("positions must be different.")
-        if max(pos) >= self.qubits_number:
-            raise PanicException("pos is out of the bound.")
-        arr = (C.c_size_t * k)(*pos)
+        arr = _qk_positions(pos, self.qubits_number)
         check(self._lib.qdc_qkgate(self._p, ptr(g), arr, k, self.qubits_number))
+
+    def apply_qk_gate_tr(self, gate, positions):
+        c = 1 << len(positions)
+        self.apply_qk_gate(self._gate(gate, c * c).reshape(c, c).T.reshape(-1), positions)
+
+    def apply_qk_gate_conj_tr(self, gate, positions):
+        c = 1 << len(positions)
+        self.apply_qk_gate(self._gate(gate, c * c).reshape(c, c).T.conj().reshape(-1), positions)
+
+    def get_qk_density(self, positions) -> np.ndarray:
+        """Reduced density matrix of 1 <= k <= 5 qubits (qdc_qkdensity, include/qdc/dense.h), a
+        1-D array of 4^k values: row-major 2^k x 2^k, local index bit (k-1-b) is qubit
+        positions[b]; at k = 1, 2 it is get_q1_density / get_q2_density bit for bit."""
+        pos = [int(p) for p in positions]
+        k = len(pos)
+        arr = _qk_positions(pos, self.qubits_number)
+        d = np.zeros(1 << (2 * k), self.dtype)
+        check(self._lib.qdc_qkdensity(self._p, ptr(d), arr, k, self.qubits_number))
+        return d
 
     def apply_q2_gate_inv(self, gate, pos2, pos1):
         g = self._gate(gate, 16)
@@ -751,3 +779,15 @@ def get_q2_grad(fwd, bwd, pos2, pos1):
 def get_q2_grad_diag(fwd, bwd, pos2, pos1):
     """quantized_tensor.rs:207-221."""
     return _grad("q2grad_diag", fwd, bwd, 4, pos2, pos1)
+
+
+def get_qk_grad(fwd, bwd, positions):
+    """Gradient of a dense gate on 1 <= k <= 5 qubits (qdc_qkgrad, include/qdc/dense.h), a 1-D
+    array of 4^k values: get_q2_grad's rule (sum over groups of bwd[r] * fwd[c], no conjugation)
+    with apply_qk_gate's index convention; at k = 1, 2 it is get_q1_grad / get_q2_grad bit for
+    bit."""
+    if fwd.qubits_number != bwd.qubits_number:
+        raise PanicException("fwd and bwd have different lengths.")
+    pos = [int(p) for p in positions]
+    arr = _qk_positions(pos, fwd.qubits_number)
+    return _grad("qdc_qkgrad", fwd, bwd, 1 << (2 * len(pos)), arr, len(pos))

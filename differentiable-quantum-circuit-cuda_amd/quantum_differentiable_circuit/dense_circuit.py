@@ -1,0 +1,139 @@
+"""A differentiable circuit of dense gates and densities on 1..5 qubits.
+
+``DenseCircuit`` has the shape and the call order of ``AbiCircuit`` (``abi_circuit.py``, which
+restates ``src/circuit.rs:164-429``), over the dense k-qubit primitives of ``include/qdc/dense.h``
+in place of the q1 / q2 ones:
+
+* forward: one ``qdc_qkgate`` per gate, ``qdc_qkdensity`` (a host sync each) per density;
+* backward, walking the instructions in reverse, per gate: ``apply_qk_gate_conj_tr`` on fwd (the
+  uncompute), then, once a cotangent has been injected, ``get_qk_grad(fwd, bwd, positions)`` for
+  a variable gate and ``apply_qk_gate_tr`` on bwd; per differentiable density:
+  ``conj_and_double`` into a new state, ``apply_qk_gate_tr(cotangent)`` on it, then ``add`` into
+  bwd (the first one becomes bwd).  Variable gates met before the first cotangent get zero
+  gradients.
+
+Gates are 1-D arrays of 4^k values (2^k x 2^k row-major, local index bit (k-1-b) = qubit
+positions[b]); densities come back as (2^k, 2^k) arrays and gradients as 1-D arrays in forward
+order.  At k = 1, 2 every call lands on the q1 / q2 kernels, so a circuit of 1- and 2-qubit
+instructions computes what ``AbiCircuit`` computes, bit for bit.
+
+Gates are assumed unitary: the uncompute applies the conjugate transpose.  Non-unitary dense
+gates would need a 2^k x 2^k LU inverse on the host and are out of scope.  No fusion: every
+instruction is one primitive call (the fused runtime, ``Circuit``, has no dense instruction
+kinds).
+"""
+from __future__ import annotations
+
+from collections import deque
+from typing import List
+
+import numpy as np
+
+from . import PanicException, QuantizedTensor, data_transfer, get_qk_grad
+from .abi_circuit import _slice
+
+CONST_GATE, VAR_GATE, DENSITY, DIFF_DENSITY = range(4)
+
+
+class DenseCircuit:
+    def __init__(self, qubits_number: int, precision: str | None = None):
+        self.initial_state = QuantizedTensor.new_standard(qubits_number, precision)
+        self.state = self.initial_state.clone()
+        self.instructions = []
+        self.dtype = self.initial_state.dtype
+        self.bwd = None
+
+    def set_state_from_vector(self, vector):
+        self.initial_state.set_from_host(np.asarray(vector, dtype=self.dtype))
+
+    # --- builders -------------------------------------------------------------------------
+    def _push(self, kind, positions):
+        pos = tuple(int(p) for p in positions)
+        if not 1 <= len(pos) <= 5:
+            raise PanicException("k must be in 1..5.")
+        if len(set(pos)) != len(pos):
+            raise PanicException("positions must be different.")
+        if max(pos) >= self.state.qubits_number:
+            raise PanicException("pos is out of the bound.")
+        self.instructions.append((kind, pos))
+
+    def add_const_gate(self, positions): self._push(CONST_GATE, positions)
+    def add_var_gate(self, positions): self._push(VAR_GATE, positions)
+    def get_dens_op(self, positions): self._push(DENSITY, positions)
+    def get_dens_op_with_grad(self, positions): self._push(DIFF_DENSITY, positions)
+
+    # --- forward --------------------------------------------------------------------------
+    def _forward(self, const_gates, var_gates, all_densities) -> List[np.ndarray]:
+        if not self.instructions:
+            raise PanicException("The circuit is empty.")
+        out = []
+        cg, vg = deque(const_gates), deque(var_gates)
+        data_transfer(self.initial_state, self.state)
+        s = self.state
+        for kind, pos in self.instructions:
+            if kind in (CONST_GATE, VAR_GATE):
+                pool = cg if kind == CONST_GATE else vg
+                if not pool:
+                    word = "constant" if kind == CONST_GATE else "variable"
+                    raise PanicException(f"The number of {word} gates is less than required.")
+                s.apply_qk_gate(_slice(pool.popleft()), pos)
+            elif kind == DIFF_DENSITY or all_densities:
+                c = 1 << len(pos)
+                out.append(s.get_qk_density(pos).reshape(c, c))
+        if cg:
+            raise PanicException("Number of constant gates is more than required.")
+        if vg:
+            raise PanicException("Number of variable gates is more than required.")
+        return out
+
+    def run(self, const_gates, var_gates):
+        """Every density matrix, in instruction order."""
+        return self._forward(const_gates, var_gates, True)
+
+    def forward(self, const_gates, var_gates):
+        """The differentiable density matrices, in instruction order."""
+        return self._forward(const_gates, var_gates, False)
+
+    # --- backward -------------------------------------------------------------------------
+    def backward(self, grads_wrt_density, const_gates, var_gates) -> List[np.ndarray]:
+        """Gradients of the variable gates, forward order; call after ``forward`` with the same
+        gates.  Leaves the forward state uncomputed back to the initial state."""
+        if not self.instructions:
+            raise PanicException("The circuit is empty.")
+        dens, cg, vg = list(grads_wrt_density), list(const_gates), list(var_gates)
+        fwd = self.state
+        bwd = None
+        grads = deque()
+        for kind, pos in reversed(self.instructions):
+            if kind in (CONST_GATE, VAR_GATE):
+                pool = cg if kind == CONST_GATE else vg
+                if not pool:
+                    raise PanicException("The number of gates is less than required.")
+                g = _slice(pool.pop())
+                fwd.apply_qk_gate_conj_tr(g, pos)
+                if bwd is not None:
+                    if kind == VAR_GATE:
+                        grads.appendleft(get_qk_grad(fwd, bwd, pos))
+                    bwd.apply_qk_gate_tr(g, pos)
+                elif kind == VAR_GATE:
+                    grads.appendleft(np.zeros(1 << (2 * len(pos)), self.dtype))
+            elif kind == DIFF_DENSITY:
+                if not dens:
+                    raise PanicException(
+                        "The number of gradients wrt density matrices is less than required.")
+                gd = _slice(dens.pop(), "Gradient is not contiguous.")
+                addition = fwd.conj_and_double()
+                addition.apply_qk_gate_tr(gd, pos)
+                if bwd is None:
+                    bwd = addition
+                else:
+                    bwd.add(addition)
+                    del addition
+        if cg:
+            raise PanicException("Number of constant gates is more than required.")
+        if vg:  # circuit.rs:426 words it this way
+            raise PanicException("Number of constant gates is more than required.")
+        if dens:
+            raise PanicException("Number of gradients wrt density matrices is more than required.")
+        self.bwd = bwd
+        return list(grads)

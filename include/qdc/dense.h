@@ -28,6 +28,19 @@ extern "C" {
 const char* qdc_qkgate(qdc_complex* state, const qdc_complex* gate, const size_t* pos, size_t k,
                        size_t n);
 
+/* The gradient and the reduced density matrix of such a gate (csrc/qdc_qkgrad.hpp), with
+ * qdc_qkgate's conventions, validation and messages; C = 2^k.  grad / density: HOST buffers of
+ * C*C values that are accumulated into (`+=`) before return, as q2grad and get_q2density do.
+ * k = 1, 2 are q1grad / q2grad(pos[0], pos[1]) and get_q1density / get_q2density, bit for bit.
+ *
+ * grad[r*C + c] += sum over groups of bwd[r] * fwd[c]   (no conjugation: q2grad's rule) */
+const char* qdc_qkgrad(const qdc_complex* fwd, const qdc_complex* bwd, qdc_complex* grad,
+                       const size_t* pos, size_t k, size_t n);
+
+/* density[r*C + c] += sum over groups of state[r] * conj(state[c])   (get_q2density's rule) */
+const char* qdc_qkdensity(const qdc_complex* state, qdc_complex* density, const size_t* pos,
+                          size_t k, size_t n);
+
 /* The primitives' stream (every entry point above is ordered on it): wait for it. */
 const char* qdc_abi_sync(void);
 
