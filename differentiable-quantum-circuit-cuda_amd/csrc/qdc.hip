@@ -541,19 +541,23 @@ static const char* spec_program_for(unsigned tile_bits, const unsigned* kinds, c
   if (n == 0 || n > 64) return "invalid arguments";
   std::vector<qdc::RqStage> st(n);
   for (size_t i = 0; i < n; ++i) st[i] = qdc::RqStage{kinds[i], t1[i], t2[i], deps ? deps[i] : 0};
-  // the runtime's tiles: f32 11 two-state (five slots), 12 one-state; f64 10 two-state, 11 one-state;
-  // tile_bits | 0x100: a one-state pass on the two-state tile size (f32: one wave, five slots)
-  // | 0x200 as well: that pass prefetching the next tile (f32 one-wave: k_rw<false, 2, true, 1, true>)
+  // the runtime's tiles: the two-state tile (f32 2^11, f64 2^10) runs a two-state pass, the next
+  // size a one-state pass, each on the variant the default knobs select (qdc_variant.hpp);
+  // tile_bits | 0x100: a one-state pass on the two-state tile size (QDC_RW bit 1)
+  // | 0x200 as well: that pass prefetching the next tile (QDC_RW bit 3)
+  // | 0x400: relayouts through the full buffer (QDC_SPEC_HALF=0)
   const bool force_one = (tile_bits & 0x100u) != 0, pf = (tile_bits & 0x200u) != 0;
-  const unsigned tile_bits_in = tile_bits;
+  const bool spec_half = !(tile_bits & 0x400u);
   tile_bits &= 0xffu;
   const unsigned t2bits = sizeof(qdc::real) == 4 ? 11u : 10u;
   if (tile_bits != t2bits && tile_bits != t2bits + 1) return "tile_bits: not a specialized pass's tile";
   const bool two = tile_bits == t2bits && !force_one;
-  const qdc::SpecKind K = two ? qdc::spec_kind_two() : qdc::spec_kind_one(tile_bits, pf);
-  const bool keep = K.ns == 5 && tile_bits == 11 && !pf && !(tile_bits_in & 0x400u) &&
-                    sizeof(qdc::real) == 4;  // (as the runtime's spec_half planning)
-  const qdc::RqPlan plan = qdc::rq_plan(st, tile_bits, nullptr, true, K.ns, keep);
+  qdc::RqKnobs knobs;
+  if (tile_bits == t2bits && force_one) knobs.rq_wave |= pf ? 2 | 8 : 2;
+  const qdc::RqVariant* V = qdc::rq_select(two, tile_bits, knobs, false);
+  if (!V || !V->prefix) return "tile_bits: not a specialized pass's tile";
+  const bool keep = spec_half && V->ns == 5;  // (build_program's planning)
+  const qdc::RqPlan plan = qdc::rq_plan(st, tile_bits, nullptr, true, V->ns, keep);
   std::vector<qdc::SpecStep> sst;
   qdc::RqLayout cur = plan.load;
   for (const qdc::RqStep& s : plan.steps) {
@@ -571,13 +575,13 @@ static const char* spec_program_for(unsigned tile_bits, const unsigned* kinds, c
       F.t1 = (s.cs & 7u) * 8u + (s.cs >> 3);  // the runtime's canonical S1 < S2
     sst.push_back(qdc::SpecStep{false, cur, cur, F});
   }
-  // (the runtime's choice: a one-wave one-state program whose relayouts all keep a slot runs on
-  // half buffers, qdc_circuit.hpp half1; | 0x400 keeps the full buffer)
-  const bool half = keep && qdc::spec_half_ok(sst);
-  const qdc::SpecKind KK = !half ? K : two ? qdc::spec_kind_two(true) : qdc::spec_kind_one(tile_bits, false, true);
-  const std::string body = qdc::spec_program_source(sst, tile_bits, KK);
-  name = qdc::spec_kernel_name(body, KK);
-  src = qdc::spec_kernel_source(name, body, KK);
+  // (build_program's choice: a program whose relayouts all keep a slot runs on half buffers
+  // where its variant has that form)
+  const bool half = V->pass_half && spec_half && !qdc::spec_imm() && qdc::spec_half_ok(sst);
+  const qdc::SpecKind K = qdc::spec_kind(*V, half);
+  const std::string body = qdc::spec_program_source(sst, tile_bits, K);
+  name = qdc::spec_kernel_name(body, K);
+  src = qdc::spec_kernel_source(name, body, K);
   return nullptr;
 }
 
@@ -790,6 +794,31 @@ QDC_API const char* qdc_spec_fingerprint(const char* defines, const char* compil
   if (!qdc::spec_source_fp(cs, cs + "/../../include", sfp)) return "cannot read the kernel headers";
   *fingerprint = qdc::spec_fingerprint(defines ? std::string(defines) : qdc::spec_defines(), compiler, sfp);
   if (source_hash) *source_hash = sfp;
+  return nullptr;
+}
+
+// Host-only test hook of the kernel-variant table (qdc_variant.hpp): the row a dry circuit
+// (init_dry: the QDC_* knobs of the environment) selects for a two- or one-state pass on
+// 2^tile_bits-amplitude tiles.  out[0..4] = {block threads, register slots, dynamic tail allowed,
+// specialized grid from its own occupancy, plans keep a slot (half buffers)}; text_out = the
+// generic kernel, the specialized pass and its half-buffer form, each NUL-ended ("": none).
+QDC_API const char* qdc_rq_variant(int two, unsigned tile_bits, unsigned* out, char* text_out,
+                                   size_t cap) {
+  if (!out || !text_out || tile_bits > 31) return qdc::fail("invalid variant arguments");
+  qdc::Circuit k;
+  QDC_TRY(k.init_dry(12, 1));
+  const qdc::RqVariant* V = nullptr;
+  QDC_TRY(k.rq_variant(two != 0, tile_bits, V));
+  const unsigned v[5] = {V->threads, V->ns, V->dyn ? 1u : 0u, V->own_grid ? 1u : 0u,
+                         k.rq_keep(*V) ? 1u : 0u};
+  for (int i = 0; i < 5; ++i) out[i] = v[i];
+  size_t w = 0;
+  for (const char* s : {V->label, V->prefix ? V->pass : "", V->pass_half ? V->pass_half : ""}) {
+    const size_t n = strlen(s) + 1;
+    if (w + n > cap) return qdc::fail("text buffer too small");
+    std::memcpy(text_out + w, s, n);
+    w += n;
+  }
   return nullptr;
 }
 

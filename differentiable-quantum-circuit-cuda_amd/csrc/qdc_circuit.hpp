@@ -241,17 +241,10 @@ struct Circuit {
     host_ms[dir][0] += 1;
     for (int k = 1; k < 6; ++k) host_ms[dir][k] += ms_between(t[k - 1], t[k]);
   }
-  int rq_prefetch = 1;      // one-state register-resident passes prefetch the next tile (QDC_RQ_PF)
-  int rq_prefetch2 = 0;     // two-state ones too (QDC_RQ_PF2; 2 waves/SIMD, measured slower)
+  // which register-resident kernel variant runs a pass (QDC_RW, QDC_RQ_PF, QDC_RQ_SLOTS5): read
+  // by rq_variant() below and nowhere else
+  RqKnobs rqk;
   int rq64 = 1;  // f64 gate passes register-resident too (k_rw; QDC_RQ64)
-  int rq_slots5 = 1;  // two-state f32 k_rw passes plan five register slots (QDC_RQ_SLOTS5)
-  // one-state f32 passes on 2^12 tiles run on two-wave, five-slot, prefetching k_rw tiles
-  // instead of four-wave, four-slot k_rq ones (QDC_RQ_FWD5)
-  int rq_fwd5 = 0;  // measured 4 % slower per pass (r3i): 16 KiB of LDS per wave caps it at 2 waves/SIMD
-  bool rq5() const { return rq_slots5 != 0 && (rq_wave & 1) && !(rq_wave & 4); }
-  // one-state one-wave five-slot passes (2^11 tiles, QDC_RW bit 1) prefetch the next tile
-  // (QDC_RW bit 3, with QDC_RQ_PF)
-  bool rw1_prefetch() const { return (rq_wave & 8) && rq_prefetch; }
   // register-resident tile order: 0 block-contiguous, 1 grid-strided, 2 block-contiguous in
   // XCD-aware block order (QDC_RQ_ORDER).  C2 n = 28, same box (profiles/r5/r5q_*): 2 is
   // +0.4-0.6 % over 0, 1 (concurrent tiles neighbours in memory) -6.5 %
@@ -274,16 +267,14 @@ struct Circuit {
   // generated kernels by pass program (key: qdc_circuit build_program), with their functions
   std::map<std::vector<uint32_t>, SpecEntry> spec_cache;
   uint64_t spec_epoch = 0;
-  int rq_wave = 1;  // one wave per register-resident tile (k_rw; QDC_RW bit 0 two-state, bit 1
-                    // one-state, bit 2 two-state with the next tile prefetched into AGPRs)
-  int rq_permute = 1;       // gate-only passes permute their tile's qubits (QDC_RQ_PERM)
+  int rq_permute = 1;      // gate-only passes permute their tile's qubits (QDC_RQ_PERM)
   int rq_perm_shard = 1;    // ... on sharded circuits too (QDC_RQ_PERM_SHARD)
   int rq_grad32 = 1;        // two-state passes hold up to FMAX_GRAD_RQ Gamma stages (QDC_RQ_GRAD32)
   int rq_maxcl = 1;         // relayouts chosen by max closure, else greedily (QDC_RQ_MAXCL)
   uint32_t rq_perm_low = 0;  // low positions a permuting pass fills, 0: default (QDC_RQ_PERM_LOW)
   int rq_gstage = 1;  // two-state passes capped by Gamma stages, not variable gates (QDC_RQ_GSTAGE)
   // one-state fused tile in chunks (QDC_TILE1_CHUNKS): TILE_CHUNKS_1, or TILE_CHUNKS_2 (f32: 2^11
-  // amplitudes, one wave per tile on k_rw with five slots when QDC_RW bit 1 is set)
+  // amplitudes; the kernels of either size: qdc_variant.hpp)
   uint32_t tile1_chunks = TILE_CHUNKS_1;
   // runs of cotangent injections whose cotangents are all diagonal become one elementwise pass
   // (k_diag_inject; QDC_DIAG_INJECT)
@@ -314,8 +305,18 @@ struct Circuit {
   bool mirror_on() const {
     return mirror && fuse && fuse_max_ops >= 2 && use_rq && (sizeof(real) == 4 || rq64);
   }
-  // one-state one-wave five-slot passes on 2^11 tiles (f32): QDC_RW bit 1, or a mirrored forward
-  bool rw1() const { return (rq_wave & 2) || mirror_on(); }
+  // The kernel variant (qdc_variant.hpp) of a register-resident pass on 2^tbits-amplitude tiles:
+  // the one selection that planning (build_program), specialization and launch (launch_rq) share
+  const char* rq_variant(bool two, uint32_t tbits, const RqVariant*& V) const {
+    V = rq_select(two, tbits, rqk, mirror_on());
+    if (!V)
+      return fail("no register-resident kernel for a %u-amplitude %s tile", 1u << tbits,
+                  two ? "two-state" : "one-state");
+    return nullptr;
+  }
+  // its five-slot passes (2^11 tiles) are planned to keep a slot in place across every relayout
+  // where they can, for the half-buffer specialized form (rq_plan keep)
+  bool rq_keep(const RqVariant& V) const { return spec_half && V.ns == 5; }
 
   // host-only dry run (init_dry): calls stop before their first launch; build_program writes
   // the pass program into dry_prog and collects the specialized kernels into dry_specs
@@ -355,6 +356,18 @@ struct Circuit {
     return nullptr;
   }
 
+  // n qubits over `world` shards (a power of two): g rank bits, nl local qubits (init, init_dry)
+  const char* set_size(uint32_t qubits, int world) {
+    n = qubits;
+    const uint32_t gg = log2_exact((size_t)world);
+    if (gg == UINT32_MAX || gg > 8) return fail("the number of shards must be a power of two <= 256");
+    g = gg;
+    if (g > 0 && n < 2 * g + 3)
+      return fail("%u qubits are too few to shard over %d ranks (need >= %u)", n, world, 2 * g + 3);
+    nl = n - g;
+    ex.world = world;
+    return nullptr;
+  }
   // world = total shards (power of two), nlocal = shards in this process.  devices: one device
   // per local shard, each shard on its own stream (nullptr: every local shard on the current
   // device and one stream).  comms: one RCCL communicator per local shard (ncclCommInitAll;
@@ -365,14 +378,7 @@ struct Circuit {
     DeviceGuard keep;
     // the communicators are owned from here on (destroy() frees them, also on a failure below)
     if (comms) ex.comms = *comms;
-    n = qubits;
-    const uint32_t gg = log2_exact((size_t)world);
-    if (gg == UINT32_MAX || gg > 8) return fail("the number of shards must be a power of two <= 256");
-    g = gg;
-    if (g > 0 && n < 2 * g + 3)
-      return fail("%u qubits are too few to shard over %d ranks (need >= %u)", n, world, 2 * g + 3);
-    nl = n - g;
-    ex.world = world;
+    QDC_TRY(set_size(qubits, world));
     ex.rank0 = rank0;
     ex.nlocal = nlocal;
     ex.comm = comm;
@@ -417,13 +423,11 @@ struct Circuit {
     if (const char* e = getenv("QDC_FUSE_MEAS")) fuse_meas = atoi(e);
     if (const char* e = getenv("QDC_RQ")) use_rq = atoi(e);
     if (const char* e = getenv("QDC_RQ_STATS")) rq_stats = atoi(e);
-    if (const char* e = getenv("QDC_RQ_PF")) rq_prefetch = atoi(e);
-    if (const char* e = getenv("QDC_RQ_PF2")) rq_prefetch2 = atoi(e);
-    if (const char* e = getenv("QDC_RW")) rq_wave = atoi(e);
+    if (const char* e = getenv("QDC_RQ_PF")) rqk.rq_prefetch = atoi(e);
+    if (const char* e = getenv("QDC_RW")) rqk.rq_wave = atoi(e);
     if (const char* e = getenv("QDC_RQ_ORDER")) rq_order = atoi(e);
     if (const char* e = getenv("QDC_RQ64")) rq64 = atoi(e);
-    if (const char* e = getenv("QDC_RQ_SLOTS5")) rq_slots5 = atoi(e);
-    if (const char* e = getenv("QDC_RQ_FWD5")) rq_fwd5 = atoi(e);
+    if (const char* e = getenv("QDC_RQ_SLOTS5")) rqk.rq_slots5 = atoi(e);
     if (const char* e = getenv("QDC_RQ_PERM")) rq_permute = atoi(e);
     if (const char* e = getenv("QDC_RQ_PERM_SHARD")) rq_perm_shard = atoi(e);
     if (const char* e = getenv("QDC_RQ_GRAD32")) rq_grad32 = atoi(e);
@@ -463,14 +467,7 @@ struct Circuit {
   // (qdc_precompile; dry-run calls return before their first launch).
   const char* init_dry(uint32_t qubits, int world) {
     dry = true;
-    n = qubits;
-    const uint32_t gg = log2_exact((size_t)world);
-    if (gg == UINT32_MAX || gg > 8) return fail("the number of shards must be a power of two <= 256");
-    g = gg;
-    if (g > 0 && n < 2 * g + 3)
-      return fail("%u qubits are too few to shard over %d ranks (need >= %u)", n, world, 2 * g + 3);
-    nl = n - g;
-    ex.world = world;
+    QDC_TRY(set_size(qubits, world));
     ex.nlocal = 1;
     layout.identity(n, g);
     return read_knobs(world, world);  // (compiles: this process's full parallelism)
@@ -780,13 +777,12 @@ struct Circuit {
     bool has_red = false;      // reduction ops (Gamma stages or densities)
     bool writes_f = false;     // gate stages (fwd changes; else fwd is only read)
     std::vector<uint32_t> grad_slots;  // reduction slot of each reduction op, in op order
-    bool rq = false;   // register-resident pass (qdc_rq.hpp): k_rq, ops include relayouts
-    bool s5 = false;   // rq with five register slots (k_rw<true, 2, false, 1, true>)
+    bool rq = false;   // register-resident pass (qdc_rq.hpp): ops include relayouts
+    const RqVariant* var = nullptr;  // rq: the kernel variant that runs it (qdc_variant.hpp)
     bool inv = false;  // a remap (type 1) run backwards: a mirrored backward undoing the forward's remap
     bool dens1 = false;  // a read-only pass of one-qubit densities only: k_dens1
     uint32_t l0 = 0;   // rq: matrix-area offset (cx) of the L0 layout descriptor
     uint32_t tbits = 0;  // amplitude bits of the tile
-    // specialized kernel of a five-slot reverse pass or a one-state forward pass (qdc_jit.hpp): name, source, function
     SpecEntry* spec = nullptr;  // specialized kernel of the pass (qdc_jit.hpp), or none
   };
   // what a mirrored backward needs from the forward call: its schedule (plan after the
@@ -1349,14 +1345,11 @@ struct Circuit {
           if (dest[t] < 4) src[dest[t]] = t;
         }
       }
-      // five register slots on the one-wave two-state f32 kernel (k_rw<.., S5>)
-      const bool s5_two = two && rq5();
-      const bool s5_one = !two && ((rq_slots5 && rw1() && it.tbits == 11) ||  // k_rw W = 1
-                                   (rq_fwd5 && it.tbits == 12));  // k_rw W = 2, prefetching
-      const uint32_t ns = (sizeof(real) == 4 && (s5_two || s5_one)) ? 5u : 4u;
-      it.s5 = ns == 5;
-      const bool keep = spec_half && ns == 5 && it.tbits == 11 && sizeof(real) == 4;
-      const RqPlan& P = rq_plan_cached(rs, it.tbits, perm ? src : nullptr, rq_maxcl != 0, ns, keep);
+      // the kernel variant that will run the pass: the plan's register slots come from it
+      QDC_TRY(rq_variant(two, it.tbits, it.var));
+      const RqVariant& V = *it.var;
+      const RqPlan& P = rq_plan_cached(rs, it.tbits, perm ? src : nullptr, rq_maxcl != 0, V.ns,
+                                       rq_keep(V));
       it.l0 = put_layout(P.load);
       {  // rqio after the load descriptor
         rqio io{};
@@ -1373,14 +1366,8 @@ struct Circuit {
       }
       uint32_t n = 0;
       it.grad_slots.clear();  // the kernel reduces Gamma stages in execution order
-      // the kernels launch_rq runs: f32 two-state five-slot k_rw, one-state prefetching k_rq on
-      // 2^12 tiles; f64 two-state k_rw on 2^10 tiles, one-state on 2^10 / 2^11
-      const bool f32 = sizeof(real) == 4;
-      const bool spec1 = spec_on() && spec_fwd && !two &&
-                         (f32 ? ((!it.s5 && it.tbits == 12 && rq_prefetch && !(rq_wave & 2)) ||
-                                 (it.s5 && it.tbits == 11 && rw1()))
-                              : (it.tbits == 10 || it.tbits == 11));
-      const bool spec = spec1 || (spec_on() && two && (f32 ? (it.s5 && rq5()) : it.tbits == 10));
+      // the variant's specialized pass (one-state passes: QDC_SPEC_FWD)
+      const bool spec = V.prefix && spec_on() && (two || spec_fwd);
       std::vector<SpecStep> sst;
       RqLayout lcur = P.load;
       it.spec = nullptr;
@@ -1425,11 +1412,9 @@ struct Circuit {
       if (spec) {
         // the source is generated once per distinct program (per process): the key is
         // everything it depends on, the layouts, stage kinds, slot cases and Γ flags
-        const bool pf1 = spec1 && it.s5 && rw1_prefetch();
-        const bool half1 = it.s5 && it.tbits == 11 && !pf1 && spec_half && !spec_imm() &&
-                           sizeof(real) == 4 && spec_half_ok(sst);
-        std::vector<uint32_t> key = {spec1 ? 1u : 2u, it.tbits, spec_imm() ? 1u : 0u,
-                                     (pf1 ? 1u : 0u) | (half1 ? 2u : 0u)};
+        const bool half = V.pass_half && spec_half && !spec_imm() && spec_half_ok(sst);
+        std::vector<uint32_t> key = {(uint32_t)(&V - rq_variants()), it.tbits, spec_imm() ? 1u : 0u,
+                                     half ? 1u : 0u};
         auto put_layout_key = [&](const RqLayout& L) {
           key.push_back(L.ns | (L.tfix ? 0x100u : 0u));
           for (uint32_t q = 0; q < RQ_SLOTS_MAX; ++q) key.push_back(L.slot[q]);
@@ -1447,7 +1432,7 @@ struct Circuit {
         }
         auto hit = spec_cache.find(key);
         if (hit == spec_cache.end()) {
-          const SpecKind K = spec1 ? spec_kind_one(it.tbits, pf1, half1) : spec_kind_two(half1);
+          const SpecKind K = spec_kind(V, half);
           const std::string body = spec_program_source(sst, it.tbits, K);
           SpecEntry e;
           e.name = spec_kernel_name(body, K);
@@ -1570,15 +1555,9 @@ struct Circuit {
     constexpr int NT = 256;
     auto kern = k_fused<TWO, TB, HASRED, WF, NT>;
     uint32_t grid = 0;
-    QDC_TRY(fused_grid(fg, (const void*)kern, NT, grid));
+    QDC_TRY(fused_grid((const void*)kern, nullptr, NT, grid));
     fgeo g = fg;
-    uint64_t tpb = 1;
-    while (tpb * grid < g.ntiles) tpb <<= 1;
-    g.tpb = (uint32_t)tpb;
-    grid = (uint32_t)((g.ntiles + tpb - 1) / tpb);
-    if (g.ngrad > 0 && grid > NBMAX) return fail("fused reduction grid %u exceeds %u", grid, NBMAX);
-    last_fused_grid = grid;
-    last_fused_ndyn = 0;
+    QDC_TRY(size_grid(ctx, g, grid, false, "fused"));
     return ctx.launch_block(name, bytes, kern, grid, (uint32_t)NT, f, b, fops, mats, g, partials,
                             stride);
   }
@@ -1600,221 +1579,76 @@ struct Circuit {
     constexpr int NT = 256;
     auto kern = k_dens1<TB, NT>;
     uint32_t grid = 0;
-    QDC_TRY(fused_grid(fg, (const void*)kern, NT, grid));
+    QDC_TRY(fused_grid((const void*)kern, nullptr, NT, grid));
     fgeo g = fg;
-    uint64_t tpb = 1;
-    while (tpb * grid < g.ntiles) tpb <<= 1;
-    g.tpb = (uint32_t)tpb;
-    grid = (uint32_t)((g.ntiles + tpb - 1) / tpb);
-    if (grid > NBMAX) return fail("density reduction grid %u exceeds %u", grid, NBMAX);
-    last_fused_grid = grid;
-    last_fused_ndyn = 0;
+    QDC_TRY(size_grid(ctx, g, grid, false, "density"));  // (ngrad = nops > 0: always a reduction)
     return ctx.launch_block(name, bytes, kern, grid, (uint32_t)NT, (const chunk*)f, fops, g,
                             partials, stride);
   }
-  // register-resident pass (qdc_rq.hpp): threads per tile = tile amplitudes / RQ_R
+  // register-resident pass (qdc_rq.hpp) on its kernel variant V (build_program's choice,
+  // qdc_variant.hpp), or on the pass's own specialized kernel where one is loaded: the same
+  // block size, tile shares and arguments either way
   const char* launch_rq(Ctx& ctx, const char* name, double bytes, const fgeo& fg, bool two,
-                        uint32_t tbits, uint32_t l0, chunk* f, chunk* b, const fop* fops,
-                        const cx* mats, cx* partials, uint64_t stride, bool s5,
+                        uint32_t tbits, const RqVariant* V, uint32_t l0, chunk* f, chunk* b,
+                        const fop* fops, const cx* mats, cx* partials, uint64_t stride,
                         hipFunction_t spec = nullptr) {
-#ifndef QDC_F64
-    const uint32_t nt = (1u << tbits) / (uint32_t)RQ_R;
-    if (!two && s5 && nt == 256) {  // two waves per 2^12 tile, five slots, prefetching
-      const void* kw = (const void*)k_rw<false, 2, true, 2, true>;
-      uint32_t grid = 0;
-      QDC_TRY(fused_grid(fg, kw, 128, grid));
-      fgeo g = fg;
-      if (!(g.ngrad == 0 && grid >= 8 && g.ntiles >= 4ull * grid && ctx.plan_dyn(g, grid))) {
-        uint64_t tpb = 1;
-        while (tpb * grid < g.ntiles) tpb <<= 1;
-        g.tpb = (uint32_t)tpb;
-        grid = (uint32_t)((g.ntiles + tpb - 1) / tpb);
-      }
-      last_fused_grid = grid;
-      last_fused_ndyn = 0;
-      return ctx.launch_block(name, bytes, k_rw<false, 2, true, 2, true>, grid, 128u, f, b, fops,
-                              mats, g, l0, partials, stride);
-    }
-    if (!two && s5 && nt == 128 && rw1_prefetch()) {  // one wave per 2^11 tile, prefetching
-      const void* kw = (const void*)k_rw<false, 2, true, 1, true>;
-      uint32_t grid = 0;
-      QDC_TRY(fused_grid(fg, kw, 64, grid));
-      fgeo g = fg;
-      if (!(g.ngrad == 0 && grid >= 8 && g.ntiles >= 4ull * grid && ctx.plan_dyn(g, grid))) {
-        uint64_t tpb = 1;
-        while (tpb * grid < g.ntiles) tpb <<= 1;
-        g.tpb = (uint32_t)tpb;
-        grid = (uint32_t)((g.ntiles + tpb - 1) / tpb);
-      }
-      last_fused_grid = grid;
-      last_fused_ndyn = 0;
-      if (spec)
-        return ctx.launch_module(name, bytes, spec, grid, 64u, f, b, fops, mats, g, l0, partials, stride);
-      return ctx.launch_block(name, bytes, k_rw<false, 2, true, 1, true>, grid, 64u, f, b, fops,
-                              mats, g, l0, partials, stride);
-    }
-    if ((two ? (rq_wave & 1) : ((rq_wave & 2) || (rw1() && nt == 128))) &&
-        (nt == 128 || (nt == 256 && !two))) {
-      // k_rw: lane l of a tile's W waves runs k_rq's threads l + 64 W e (e < 2)
-      const bool pfw = two && (rq_wave & 4);
-      const uint32_t bs = (!two && nt == 256) ? 128u : 64u;
-      if (s5 && !((two && !pfw) || (!two && nt == 128)))
-        return fail("internal: a five-slot pass without its kernel");
-      const void* kw = two ? (pfw  ? (const void*)k_rw<true, 2, true, 1>
-                              : s5 ? (const void*)k_rw<true, 2, false, 1, true>
-                                   : (const void*)k_rw<true, 2, false, 1>)
-                           : nt == 128 ? (s5 ? (const void*)k_rw<false, 2, false, 1, true>
-                                             : (const void*)k_rw<false, 2, false, 1>)
-                                       : (const void*)k_rw<false, 2, false, 2>;
-      uint32_t grid = 0;
-      QDC_TRY(fused_grid(fg, kw, (int)bs, grid));
-      if (nt == 128 && s5 && spec && !(two && pfw)) QDC_TRY(fused_grid_fn(spec, (int)bs, grid));
-      fgeo g = fg;
-      // one wave per block: static shares + a dynamic tail
-      if (!(bs == 64 && !pfw && grid >= 8 && g.ntiles >= 4ull * grid && ctx.plan_dyn(g, grid))) {
-        uint64_t tpb = 1;
-        while (tpb * grid < g.ntiles) tpb <<= 1;
-        g.tpb = (uint32_t)tpb;
-        grid = (uint32_t)((g.ntiles + tpb - 1) / tpb);
-      }
-      if (g.ngrad > 0 && grid > NBMAX) return fail("fused reduction grid %u exceeds %u", grid, NBMAX);
-      last_fused_grid = grid;
-      last_fused_ndyn = g.ndyn ? ctx.last_ndyn : 0u;
-      if (two && pfw)
-        return ctx.launch_block(name, bytes, k_rw<true, 2, true, 1>, grid, bs, f, b, fops, mats, g,
-                                l0, partials, stride);
-      if (two && s5 && spec)  // the pass's straight-line kernel (same resources and grid)
-        return ctx.launch_module(name, bytes, spec, grid, bs, f, b, fops, mats, g, l0, partials,
-                                 stride);
-      if (two && s5)
-        return ctx.launch_block(name, bytes, k_rw<true, 2, false, 1, true>, grid, bs, f, b, fops,
-                                mats, g, l0, partials, stride);
-      if (two)
-        return ctx.launch_block(name, bytes, k_rw<true, 2, false, 1>, grid, bs, f, b, fops, mats, g,
-                                l0, partials, stride);
-      if (nt == 128 && s5 && spec)  // one-wave one-state pass, specialized
-        return ctx.launch_module(name, bytes, spec, grid, bs, f, b, fops, mats, g, l0, partials,
-                                 stride);
-      if (nt == 128 && s5)
-        return ctx.launch_block(name, bytes, k_rw<false, 2, false, 1, true>, grid, bs, f, b, fops,
-                                mats, g, l0, partials, stride);
-      if (nt == 128)
-        return ctx.launch_block(name, bytes, k_rw<false, 2, false, 1>, grid, bs, f, b, fops, mats, g,
-                                l0, partials, stride);
-      return ctx.launch_block(name, bytes, k_rw<false, 2, false, 2>, grid, bs, f, b, fops, mats, g,
-                              l0, partials, stride);
-    }
-    const void* kern = nullptr;
-    // the next tile's loads are in flight while this tile's stages run (2 waves/SIMD)
-    const bool pf = two ? rq_prefetch2 != 0 : rq_prefetch != 0;
-    if (two && nt == 128) kern = pf ? (const void*)k_rq<true, 128, true> : (const void*)k_rq<true, 128, false>;
-    else if (!two && nt == 128) kern = pf ? (const void*)k_rq<false, 128, true> : (const void*)k_rq<false, 128, false>;
-    else if (!two && nt == 256) kern = pf ? (const void*)k_rq<false, 256, true> : (const void*)k_rq<false, 256, false>;
-    else return fail("no register-resident kernel for a %u-amplitude %s tile", 1u << tbits,
-                     two ? "two-state" : "one-state");
+    if (!V || V->two != two || V->tbits != tbits || (spec && !V->prefix))
+      return fail("internal: a register-resident pass without its kernel variant");
+    // a register-resident pass holds gate stages only (build_program), and only two-state
+    // stages accumulate Gamma: a one-state pass never reduces.  Its dynamic tail (no granule
+    // partials) and the one-state kernels (no reduction code) rest on that.
+    if (!two && fg.ngrad > 0)
+      return fail("internal: a one-state register-resident pass with %u reductions", fg.ngrad);
     uint32_t grid = 0;
-    QDC_TRY(fused_grid(fg, kern, (int)nt, grid));
+    QDC_TRY(fused_grid((const void*)V->kernel, spec && V->own_grid ? spec : nullptr, (int)V->threads,
+                       grid));
     fgeo g = fg;
-    // one-state prefetching passes: static shares + a dynamic tail (no reductions here)
-    if (!(!two && pf && g.ngrad == 0 && grid >= 8 && g.ntiles >= 4ull * grid &&
-          ctx.plan_dyn(g, grid))) {
-      uint64_t tpb = 1;
-      while (tpb * grid < g.ntiles) tpb <<= 1;
-      g.tpb = (uint32_t)tpb;
-      grid = (uint32_t)((g.ntiles + tpb - 1) / tpb);
-    }
-    if (g.ngrad > 0 && grid > NBMAX) return fail("fused reduction grid %u exceeds %u", grid, NBMAX);
-    last_fused_grid = grid;
-    last_fused_ndyn = 0;
-    if (!two && nt == 256 && pf && spec)  // the pass's straight-line kernel (same resources and grid)
-      return ctx.launch_module(name, bytes, spec, grid, nt, f, b, fops, mats, g, l0, partials, stride);
-#define QDC_RQ_LAUNCH(T, N, P)                                                            \
-  if (two == T && nt == N && pf == P)                                                     \
-    return ctx.launch_block(name, bytes, k_rq<T, N, P>, grid, nt, f, b, fops, mats, g, l0, \
+    QDC_TRY(size_grid(ctx, g, grid, V->dyn, "fused"));
+    if (spec)
+      return ctx.launch_module(name, bytes, spec, grid, V->threads, f, b, fops, mats, g, l0, partials,
+                               stride);
+    return ctx.launch_block(name, bytes, V->kernel, grid, V->threads, f, b, fops, mats, g, l0,
                             partials, stride);
-    QDC_RQ_LAUNCH(true, 128, false)
-    QDC_RQ_LAUNCH(true, 128, true)
-    QDC_RQ_LAUNCH(false, 128, true)
-    QDC_RQ_LAUNCH(false, 128, false)
-    QDC_RQ_LAUNCH(false, 256, true)
-    QDC_RQ_LAUNCH(false, 256, false)
-#undef QDC_RQ_LAUNCH
-    return fail("no register-resident kernel launched");
-#else
-    // f64: 16 amplitudes (4 VGPRs each) per lane and state; two-state 2^10-amplitude tiles on one
-    // wave, one-state 2^11 on two
-    // (a reverse sweep's passes before the first injection are one-state on 2^10 tiles: one wave)
-    const uint32_t nt = (1u << tbits) / (uint32_t)RQ_R;
-    if (!(two ? nt == 64 : (nt == 64 || nt == 128)))
-      return fail("no register-resident kernel for a %u-amplitude %s tile", 1u << tbits,
-                  two ? "two-state" : "one-state");
-    const void* kw = two        ? (const void*)k_rw<true, 1, false, 1>
-                     : nt == 64 ? (const void*)k_rw<false, 1, false, 1>
-                                : (const void*)k_rw<false, 1, false, 2>;
-    const uint32_t bs = nt;
-    uint32_t grid = 0;
-    QDC_TRY(fused_grid(fg, kw, (int)bs, grid));
-    fgeo g = fg;
-    // one wave per block: static shares + a dynamic tail
-    if (!(bs == 64 && grid >= 8 && g.ntiles >= 4ull * grid && ctx.plan_dyn(g, grid))) {
-      uint64_t tpb = 1;
-      while (tpb * grid < g.ntiles) tpb <<= 1;
-      g.tpb = (uint32_t)tpb;
-      grid = (uint32_t)((g.ntiles + tpb - 1) / tpb);
-    }
-    if (g.ngrad > 0 && grid > NBMAX) return fail("fused reduction grid %u exceeds %u", grid, NBMAX);
-    last_fused_grid = grid;
-    last_fused_ndyn = g.ndyn ? ctx.last_ndyn : 0u;
-    if (spec)  // the pass's straight-line kernel (same resources and grid)
-      return ctx.launch_module(name, bytes, spec, grid, bs, f, b, fops, mats, g, l0, partials, stride);
-    if (two)
-      return ctx.launch_block(name, bytes, k_rw<true, 1, false, 1>, grid, bs, f, b, fops, mats, g, l0,
-                              partials, stride);
-    if (nt == 64)
-      return ctx.launch_block(name, bytes, k_rw<false, 1, false, 1>, grid, bs, f, b, fops, mats, g, l0,
-                              partials, stride);
-    return ctx.launch_block(name, bytes, k_rw<false, 1, false, 2>, grid, bs, f, b, fops, mats, g, l0,
-                            partials, stride);
-#endif
   }
-  // one wave of resident blocks (occupancy query, cached per kernel), or QDC_FUSED_BLOCKS
-  // (a specialized kernel: its own occupancy, which may differ from the interpreted one's)
-  const char* fused_grid_fn(hipFunction_t fn, int nt, uint32_t& grid) {
+  // One wave of resident blocks of a kernel (occupancy query, cached per kernel), or
+  // QDC_FUSED_BLOCKS.  fn: a loaded specialized kernel asked for its own occupancy instead (it
+  // may differ from the interpreted kernel's).
+  const char* fused_grid(const void* kernel, hipFunction_t fn, int nt, uint32_t& grid) {
     if (fused_blocks) {
       grid = fused_blocks;
       return nullptr;
     }
-    const void* key = (const void*)fn;
+    const void* key = fn ? (const void*)fn : kernel;
     for (auto& e : fused_resident_cache)
       if (e.first == key) {
         grid = e.second;
         return nullptr;
       }
     int per_cu = 0, dev = 0, cus = 0;
-    QDC_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, 0));
+    if (fn)
+      QDC_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, nt, 0));
+    else
+      QDC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nt, 0));
     QDC_HIP(hipGetDevice(&dev));
     QDC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     grid = (uint32_t)std::max(1, std::min(per_cu * cus, (int)NBMAX));
     fused_resident_cache.push_back({key, grid});
     return nullptr;
   }
-  const char* fused_grid(const fgeo& fg, const void* kernel, int nt, uint32_t& grid) {
-    if (fused_blocks) {
-      grid = fused_blocks;
-      return nullptr;
+  // The tile shares of a fused launch over g.ntiles tiles, from `grid` resident blocks: static
+  // shares + a dynamic tail where the kernel takes one (dyn) and Ctx::plan_dyn finds one, else a
+  // power-of-two number of tiles per block on the fewest blocks that need.  Sets g's shares and
+  // `grid`, and records the launch's grid and granule partials for the reduction slots' commit.
+  const char* size_grid(Ctx& ctx, fgeo& g, uint32_t& grid, bool dyn, const char* what) {
+    if (!(dyn && grid >= 8 && g.ntiles >= 4ull * grid && ctx.plan_dyn(g, grid))) {
+      uint64_t tpb = 1;
+      while (tpb * grid < g.ntiles) tpb <<= 1;
+      g.tpb = (uint32_t)tpb;
+      grid = (uint32_t)((g.ntiles + tpb - 1) / tpb);
     }
-    for (auto& e : fused_resident_cache)
-      if (e.first == kernel) {
-        grid = e.second;
-        return nullptr;
-      }
-    int per_cu = 0, dev = 0, cus = 0;
-    QDC_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nt, 0));
-    QDC_HIP(hipGetDevice(&dev));
-    QDC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    grid = (uint32_t)std::max(1, std::min(per_cu * cus, (int)NBMAX));
-    fused_resident_cache.push_back({kernel, grid});
-    (void)fg;
+    if (g.ngrad > 0 && grid > NBMAX) return fail("%s reduction grid %u exceeds %u", what, grid, NBMAX);
+    last_fused_grid = grid;
+    last_fused_ndyn = g.ndyn ? ctx.last_ndyn : 0u;
     return nullptr;
   }
 
@@ -1857,8 +1691,8 @@ struct Circuit {
       const uint64_t stride = (uint64_t)NBMAX * RED;
       ctx.next_flops = flops;
       if (it.rq) {
-        QDC_TRY(launch_rq(ctx, name, bytes, fg, two, it.tbits, it.l0, f, b, fops, mats, parts, stride,
-                          it.s5, spec_fn_on(it, ctx.device)));
+        QDC_TRY(launch_rq(ctx, name, bytes, fg, two, it.tbits, it.var, it.l0, f, b, fops, mats, parts,
+                          stride, spec_fn_on(it, ctx.device)));
       } else if (two) {
         if (it.writes_f)
           QDC_TRY((launch_fused<true, true, true>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride)));

@@ -1,6 +1,7 @@
-// qdc_jit.hpp — the specialized pass kernels (qdc_spec.hpp; two-state reverse passes and
-// one-state forward passes): source per pass program, compiled with hipcc for gfx950 on first
-// use, cached on disk and per device.
+// qdc_jit.hpp — the specialized pass kernels (qdc_spec.hpp): source per pass program, compiled
+// with hipcc for gfx950 on first use, cached on disk and per device.  Which kernel variants
+// have a specialized pass, and its template arguments, block size and waves, is one column of
+// the variant table (qdc_variant.hpp).
 //
 // A pass program becomes a functor of straight-line stage calls.  Its kernel is named by the
 // hash of its source and of the build fingerprint (the library's -D switches, hipcc's path and
@@ -45,6 +46,7 @@
 #include <vector>
 
 #include "qdc_fusion.hpp"
+#include "qdc_variant.hpp"
 
 extern char** environ;
 
@@ -87,49 +89,14 @@ struct SpecKind {
   const char* waves;   // amdgpu_waves_per_eu of the generic kernel
   bool half = false;   // relayouts through half the buffer (spec_xchg_half)
 };
-#ifndef QDC_F64
-// k_rw<true, 2, false, 1, true>: f32 two-state, one wave, five slots
-inline SpecKind spec_kind_two(bool half = false) {
-  if (half)  // every relayout in two rounds through half the buffer
-    return {true, 6, 5, false, "qdc_spec_", "qdc::rw_pass<true, 2, false, 1, true, Prog, true>", 64,
-            "QDC_RW_WAVES, QDC_RW_WAVES", true};
-  return {true, 6, 5, false, "qdc_spec_", "qdc::rw_pass<true, 2, false, 1, true, Prog>", 64,
-          "QDC_RW_WAVES, QDC_RW_WAVES"};
+// The specialized pass of a variant (qdc_variant.hpp; V.prefix != nullptr), or its half-buffer
+// form (V.pass_half != nullptr): every relayout in two rounds through half the buffer.
+inline SpecKind spec_kind(const RqVariant& V, bool half = false) {
+  uint32_t tb = 0;
+  while ((1u << tb) < V.threads) ++tb;
+  return {V.two, tb, V.ns, V.threads > 64, V.prefix, half ? V.pass_half : V.pass, V.threads,
+          half ? V.waves_half : V.waves, half};
 }
-// k_rq<false, 256, true>: f32 one-state 2^12 tiles, four waves, prefetching; k_rw<false, 2,
-// false, 1, true>: 2^11 tiles (QDC_TILE1_CHUNKS=1024, QDC_RW bit 1), one wave, five slots
-// (pf: the next tile prefetched into pinned VGPRs, k_rw<false, 2, true, 1, true>, QDC_RW bit 3)
-inline SpecKind spec_kind_one(uint32_t T, bool pf = false, bool half = false) {
-  // every relayout in two rounds through half the buffer (8 KiB of LDS per wave): compiled for
-  // QDC_RW_WAVES_HALF_ONE [5] waves per SIMD, which LDS now allows (~96 VGPRs, a few spilled;
-  // 4 waves at 106 VGPRs measured 0.7-1.0 % slower per step, profiles/r4s)
-  if (T == 11 && half && !pf)
-    return {false, 6, 5, false, "qdc_specf_", "qdc::rw_pass<false, 2, false, 1, true, Prog, true>", 64,
-            "QDC_RW_WAVES_HALF_ONE, QDC_RW_WAVES_HALF_ONE", true};
-  if (T == 11 && pf)
-    return {false, 6, 5, false, "qdc_specf_", "qdc::rw_pass<false, 2, true, 1, true, Prog>", 64,
-            "QDC_RW_WAVES, QDC_RW_WAVES"};
-  if (T == 11)
-    return {false, 6, 5, false, "qdc_specf_", "qdc::rw_pass<false, 2, false, 1, true, Prog>", 64,
-            "QDC_RW_WAVES_ONE, QDC_RW_WAVES_ONE"};
-  return {false, 8, 4, true, "qdc_specf_", "qdc::rq_pass<false, 256, true, Prog>", 256,
-          "QDC_RQ_PF_WAVES"};
-}
-#else
-// k_rw<true, 1, false, 1>: f64 two-state, one wave
-inline SpecKind spec_kind_two(bool = false) {
-  return {true, 6, 4, false, "qdc_spec_d_", "qdc::rw_pass<true, 1, false, 1, false, Prog>", 64,
-          "QDC_RW_WAVES, QDC_RW_WAVES"};
-}
-// k_rw<false, 1, false, W>: f64 one-state, W = 1 (2^10 tiles) or 2 (2^11)
-inline SpecKind spec_kind_one(uint32_t T, bool = false, bool = false) {
-  if (T == 10)
-    return {false, 6, 4, false, "qdc_specf_d_", "qdc::rw_pass<false, 1, false, 1, false, Prog>", 64,
-            "QDC_RW_WAVES_ONE, QDC_RW_WAVES_ONE"};
-  return {false, 7, 4, true, "qdc_specf_d_", "qdc::rw_pass<false, 1, false, 2, false, Prog>", 128,
-          "QDC_RW_WAVES_ONE, QDC_RW_WAVES_ONE"};
-}
-#endif
 // The register slot a relayout keeps (the same tile bit in the same slot of both layouts), or
 // -1: a half-buffer relayout splits on it (spec_xchg_half).
 inline int spec_kept_slot(const RqLayout& Lc, const RqLayout& Ln) {

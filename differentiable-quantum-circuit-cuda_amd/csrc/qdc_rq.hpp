@@ -22,6 +22,10 @@
 // tile bit 0 (the two amplitudes of a 16-B chunk), slots 1..3 = the top three tile bits, thread
 // bits = tile bits 1..T-4 — so register pair (2i, 2i+1) is chunk t + i*NT, as in k_fused, and
 // loads/stores go straight between HBM and registers.  Every program ends in L0.
+//
+// The kernels (k_rq: a tile per block of NT threads; k_rw: a tile per wave, or two) are
+// templates; the instances the runtime launches, with their tile, block size, register slots
+// and the knobs that select them, are the rows of one host-side table (qdc_variant.hpp).
 #pragma once
 
 #include <type_traits>
@@ -614,18 +618,17 @@ __device__ __forceinline__ void rq_pass(chunk* __restrict__ f, chunk* __restrict
       store(xf, xb, base);
     }
   } else {
-    // the next tile's chunks (pf_f, pf_b) are in flight while this tile (xf, xb) runs
+    // the next tile's chunks (pf_f) are in flight while this tile (xf) runs
+    static_assert(!TWO, "k_rq prefetch: one-state passes (qdc_variant.hpp)");
+    // (f32 only: written in terms of TWO so that an f64 build, which never instantiates this
+    // branch, does not check the call below against its 16 chunks per thread)
     constexpr int NLD = TWO ? 2 * CPT : CPT;  // vector-memory ops per tile: loads = stores
-    vec16 pf_f[CPT], pf_b[CPT];
-    cx xf[RQ_R], xb[RQ_R];
+    vec16 pf_f[CPT];
+    cx xf[RQ_R], xb[RQ_R];  // xb unused (eliminated)
     auto issue = [&](uint64_t base) __attribute__((always_inline)) {
       const rqio* rg = rqio_now();
       const chunk* pf = f + (base + thr_ld);
-      const chunk* pb = b + (base + thr_ld);
-      constexpr int BASE = TWO ? RQ_PIN_TWO : RQ_PIN_ONE;
-#define QDC_RQ_ISSUE(i)                                                                   \
-  pf_f[i] = rq_ld<BASE + 4 * (i)>(pf + rg->offi_ld[i]);                                   \
-  if constexpr (TWO) pf_b[i] = rq_ld<RQ_PIN_TWO + 32 + 4 * (i)>(pb + rg->offi_ld[i]);
+#define QDC_RQ_ISSUE(i) pf_f[i] = rq_ld<RQ_PIN_ONE + 4 * (i)>(pf + rg->offi_ld[i]);
       static_assert(CPT == 8, "eight chunks per state and thread");
       QDC_RQ_ISSUE(0) QDC_RQ_ISSUE(1) QDC_RQ_ISSUE(2) QDC_RQ_ISSUE(3)
       QDC_RQ_ISSUE(4) QDC_RQ_ISSUE(5) QDC_RQ_ISSUE(6) QDC_RQ_ISSUE(7)
@@ -637,11 +640,6 @@ __device__ __forceinline__ void rq_pass(chunk* __restrict__ f, chunk* __restrict
         const chunk c = __builtin_bit_cast(chunk, pf_f[i]);
         xf[2 * i] = c.v[0];
         xf[2 * i + 1] = c.v[1];
-        if constexpr (TWO) {
-          const chunk d = __builtin_bit_cast(chunk, pf_b[i]);
-          xb[2 * i] = d.v[0];
-          xb[2 * i + 1] = d.v[1];
-        }
       }
     };
     // Dynamic tail (one-state passes, fgeo::ndyn): after its count static tiles the block takes
@@ -689,10 +687,7 @@ __device__ __forceinline__ void rq_pass(chunk* __restrict__ f, chunk* __restrict
       // younger than tile s-1's loads: tile s-2's stores (none before the second tile; at s = 0
       // nothing is in flight and take() reads registers nothing uses).  Unconditional, so every
       // path from an issue to the next read of its registers passes this wait.
-      if constexpr (TWO)
-        rq_vmwait_two<NLD>(s <= 1 ? 1u : 0u, pf_f, pf_b);
-      else
-        rq_vmwait_one<NLD>(s <= 1 ? 1u : 0u, pf_f);
+      rq_vmwait_one<NLD>(s <= 1 ? 1u : 0u, pf_f);
       take();
       const uint64_t prev = cur;
       uint64_t tile = 0;
@@ -725,6 +720,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PF ? QDC_RQ_
 void k_rq(chunk* __restrict__ f, chunk* __restrict__ b, const fop* __restrict__ ops,
           const cx* __restrict__ mats, fgeo fg, uint32_t l0, cx* __restrict__ partials,
           uint64_t slot_stride) {
+  // the instances the runtime launches (the rows of qdc_variant.hpp): two-state 2^11 tiles
+  // without prefetch, one-state 2^11 / 2^12 tiles with and without
+  static_assert(TWO ? (NT == 128 && !PF) : (NT == 128 || NT == 256), "k_rq: not a launched variant");
   rq_pass<TWO, NT, PF>(f, b, ops, mats, fg, l0, partials, slot_stride);
 }
 
@@ -754,12 +752,10 @@ void k_rq(chunk* __restrict__ f, chunk* __restrict__ b, const fop* __restrict__ 
 // S5: five-slot layouts (NE = 2, W = 1): the register-group bit is register slot 4, which
 // stages address like the other four, so covers hold 5 qubits (fewer relayouts); the layout
 // descriptor then spans all 32 registers (rp[16 e + j], chunk offsets offi[8 e + i]).
-// One-state forward passes on 2^12-amplitude tiles (round 3): W = 2, NE = 2, S5 and PF — two
-// waves per tile, 32 amplitudes per lane, five register slots (k_rq's one-state tiles hold 16
-// per thread: four slots, and a third of the forward's VALU time went to relayouts with their
-// four-wave barriers), and the next tile's 16 chunks per lane prefetched into pinned VGPRs as in
-// k_rq (rq_ld / rq_vmwait_two), with a dynamic tail taken block-wide.
-// PROG (not void; non-prefetching instances): the pass program as straight-line stage calls
+// One-state S5 passes with PF (2^11-amplitude tiles, W = 1): the next tile's 16 chunks per lane
+// prefetched into pinned VGPRs as in k_rq (rq_ld / rq_vmwait_two), with a dynamic tail taken
+// block-wide.
+// PROG (not void; not the two-state prefetching instance): the pass program as straight-line stage calls
 // (qdc_spec.hpp) in place of the interpreted op loop.
 template <bool TWO, int NE, bool PF, int W, bool S5 = false, class PROG = void, bool HALF = false>
 __device__ __forceinline__ void rw_pass(chunk* __restrict__ f, chunk* __restrict__ b,
@@ -767,8 +763,8 @@ __device__ __forceinline__ void rw_pass(chunk* __restrict__ f, chunk* __restrict
                                         fgeo fg, uint32_t l0, cx* __restrict__ partials,
                                         uint64_t slot_stride) {
   static_assert(NE == 1 || NE == 2 || NE == 4, "k_rw: 1, 2 or 4 register groups");
-  static_assert(!S5 || (NE == 2 && VEC == 2 && ((W == 1 && (!PF || !TWO)) || (W == 2 && PF && !TWO))),
-                "five slots: f32 one-wave tiles, or the prefetching one-state tiles");
+  static_assert(!S5 || (NE == 2 && VEC == 2 && W == 1 && (!PF || !TWO)),
+                "five slots: f32 one-wave tiles (two-state ones without prefetch)");
   static_assert(W == 1 || (W == 2 && !TWO), "k_rw: two-state tiles are one wave");
   constexpr int LOGNE = NE == 1 ? 0 : NE == 2 ? 1 : 2;
   constexpr int TB = W == 1 ? 6 : 7;  // k_rq thread bits held by the block's threads
@@ -1005,11 +1001,11 @@ __device__ __forceinline__ void rw_pass(chunk* __restrict__ f, chunk* __restrict
       tile(t);
     }
   } else if constexpr (!TWO) {
-    // one-state prefetch (W = 1 or 2, NE = 2, S5): this lane's 16 chunks of the next tile in flight in
+    // one-state prefetch (W = 1, NE = 2, S5): this lane's 16 chunks of the next tile in flight in
     // pinned v[192:255] while this tile runs; step s takes tile s-1, issues tile s, runs and
     // stores tile s-1 (k_rq's PF loop, with k_rw's register groups)
-    static_assert(NE == 2 && (W == 1 || W == 2) && S5 && CPT == 16,
-                  "one-state prefetch: S5 tiles of 2^11 (one wave) or 2^12 (two waves) amplitudes");
+    static_assert(NE == 2 && W == 1 && S5 && CPT == 16,
+                  "one-state prefetch: S5 tiles of 2^11 amplitudes (one wave)");
     constexpr int NLD = CPT;  // vector-memory ops per tile: loads = stores
     vec16 pf_a[8], pf_b[8];   // chunks 0..7 (register group 0) and 8..15 (group 1)
     auto issue = [&](uint64_t base) __attribute__((always_inline)) {
@@ -1147,6 +1143,14 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(
 void k_rw(chunk* __restrict__ f, chunk* __restrict__ b, const fop* __restrict__ ops,
           const cx* __restrict__ mats, fgeo fg, uint32_t l0, cx* __restrict__ partials,
           uint64_t slot_stride) {
+  // the instances the runtime launches (the rows of qdc_variant.hpp).  f32 (NE = 2): two-state
+  // one-wave tiles with four slots (also prefetching into AGPRs) or five; one-state one-wave
+  // tiles with four slots, or five (also prefetching); one-state two-wave tiles with four.
+  // f64 (NE = 1): two-state one-wave tiles, one-state tiles of one or two waves.
+  static_assert(NE == 2 ? (VEC == 2 && (TWO ? (W == 1 && !(PF && S5))
+                                            : (W == 1 ? (!PF || S5) : (W == 2 && !PF && !S5))))
+                        : (NE == 1 && VEC == 1 && !PF && !S5 && (W == 1 || (W == 2 && !TWO))),
+                "k_rw: not a launched variant");
   rw_pass<TWO, NE, PF, W, S5>(f, b, ops, mats, fg, l0, partials, slot_stride);
 }
 

@@ -425,6 +425,23 @@ def rq_plan(tile_bits, stages, deps=None, precision=None, slots=4):
     return rows[0][3:3 + slots], steps, rows[-1][3:3 + slots]
 
 
+def rq_variant(two, tile_bits, precision="f32"):
+    """The register-resident kernel variant (csrc/qdc_variant.hpp) the runtime selects for a
+    two- or one-state pass on 2^tile_bits-amplitude tiles under the QDC_* knobs of the
+    environment (qdc_rq_variant, host only).  Returns a dict: kernel, threads, slots, dyn, spec
+    (the specialized pass or ""), spec_half (its half-buffer form or ""), own_grid, keep; raises
+    RuntimeError with the runtime's message when no kernel runs such a tile."""
+    lib = load(precision)
+    out = (C.c_uint * 5)()
+    text = C.create_string_buffer(512)
+    err = lib.qdc_rq_variant(int(bool(two)), int(tile_bits), out, text, 512)
+    if err:
+        raise RuntimeError(err.decode())
+    kernel, spec, half = (s.decode() for s in text.raw.split(b"\0")[:3])
+    return {"kernel": kernel, "threads": int(out[0]), "slots": int(out[1]), "dyn": bool(out[2]),
+            "spec": spec, "spec_half": half, "own_grid": bool(out[3]), "keep": bool(out[4])}
+
+
 def spec_selftest(tile_bits, stages, deps=None, precision="f32"):
     """Compile the specialized kernel of a pass (host only: the runtime's generator and hipcc,
     qdc_spec_selftest): f32 tile_bits 11, a five-slot two-state reverse pass; 12, a four-slot

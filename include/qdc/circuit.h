@@ -221,6 +221,16 @@ size_t qdc_rq_plan(unsigned tile_bits, unsigned slots, const unsigned* kinds, co
                    const unsigned* t2, const unsigned long long* deps, size_t n,
                    unsigned* steps, size_t cap);
 
+/* Test hook (host only): the register-resident kernel variant (csrc/qdc_variant.hpp) the
+ * runtime selects, under the QDC_* knobs of the environment, for a two-state (two != 0) or
+ * one-state pass on tiles of 2^tile_bits amplitudes.  out[0..4] = {block threads, register
+ * slots, 1 if the launch may use a dynamic tail, 1 if a specialized launch sizes its grid from
+ * the specialized kernel's own occupancy (0: the generic kernel's), 1 if the pass is planned
+ * for half-buffer relayouts}; text_out receives three NUL-ended strings: the generic kernel,
+ * the specialized pass ("": none) and its half-buffer form ("": none).  Returns NULL, or the
+ * error a pass on such a tile gets. */
+const char* qdc_rq_variant(int two, unsigned tile_bits, unsigned* out, char* text_out, size_t cap);
+
 /* Test hook (host only): the specialized kernel of a pass over n stages (kinds / t1 / t2 / deps
  * as qdc_rq_plan) — f32 tile_bits 11: a five-slot two-state reverse pass, every stage
  * accumulating Gamma; 12: a four-slot one-state forward pass; f64: 10 two-state, 11 one-state: the

@@ -168,16 +168,18 @@ def build_env(prec, n, ins, env):
     return c
 
 
-# register-resident variants (csrc/qdc_rq.hpp): k_rq (a tile per block of NT threads, QDC_RW=0),
-# k_rw (a tile per wave; bit 0 two-state, bit 1 one-state, bit 2 two-state with the next tile
-# prefetched into AGPRs), the grid-strided tile order, and block-contiguous tiles in XCD-aware
-# block order
+# register-resident variants: knob settings that between them reach the rows of the kernel
+# table (csrc/qdc_variant.hpp, which says which knob selects which kernel;
+# tests/test_rq_variant.py checks the selection on the CPU), the grid-strided tile order, and
+# block-contiguous tiles in XCD-aware block order
 RQ_VARIANTS = {
     "lds": {"QDC_RQ": 0},
     "k_rq": {"QDC_RQ": 1, "QDC_RW": 0},
+    "k_rq_nopf": {"QDC_RQ": 1, "QDC_RW": 0, "QDC_RQ_PF": 0},
     "k_rw": {"QDC_RQ": 1, "QDC_RW": 1},
     "k_rw_all": {"QDC_RQ": 1, "QDC_RW": 3},
     "k_rw_pf": {"QDC_RQ": 1, "QDC_RW": 5},
+    "k_rw_pf1": {"QDC_RQ": 1, "QDC_RW": 9},
     "k_rw_gstride": {"QDC_RQ": 1, "QDC_RW": 1, "QDC_RQ_ORDER": 1},
     "k_rw_xcd": {"QDC_RQ": 1, "QDC_RW": 1, "QDC_RQ_ORDER": 2},
 }
