@@ -11,9 +11,11 @@
 
 #include "qdc/circuit.h"
 #include "qdc/dense.h"
+#include "qdc/pauli.h"
 #include "qdc_device.hpp"
 #include "qdc_qk.hpp"
 #include "qdc_qkgrad.hpp"
+#include "qdc_pauli.hpp"
 
 namespace qdc {
 
@@ -367,6 +369,51 @@ __attribute__((visibility("default"))) const char* qdc_qkdensity(const qdc_compl
   static qdc::QkgScratch scratch[qdc::ABI_MAX_DEVICES];  // guarded by the ABI mutex
   return qdc::reduce_qk(ctx, s, nullptr, density, pos, (uint32_t)k, (uint32_t)n,
                         scratch[ctx.device]);
+}
+
+// ---- Pauli-sum observables (include/qdc/pauli.h, qdc_pauli.hpp) ------------------------------
+
+__attribute__((visibility("default"))) const char* qdc_pauli_energy(
+    const qdc_complex* state, const unsigned long long* xmask, const unsigned long long* zmask,
+    const double* coeff, size_t terms, size_t n, double* energy) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  qdc::PauliPlan plan;
+  QDC_TRY(qdc::pauli_plan(xmask, zmask, coeff, terms, n, plan));
+  return qdc::pauli_energy(ctx, reinterpret_cast<const qdc::cx*>(state), plan, (uint32_t)n, energy);
+}
+
+__attribute__((visibility("default"))) const char* qdc_pauli_inject(
+    const qdc_complex* fwd, qdc_complex* bwd, const unsigned long long* xmask,
+    const unsigned long long* zmask, const double* coeff, size_t terms, size_t n, double weight,
+    int accumulate) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  qdc::PauliPlan plan;
+  QDC_TRY(qdc::pauli_plan(xmask, zmask, coeff, terms, n, plan));
+  if (!std::isfinite(weight)) return qdc::fail("Pauli coefficients must be finite.");
+  if (fwd == bwd) return qdc::fail("fwd and bwd must be different states.");
+  return qdc::pauli_inject(ctx, reinterpret_cast<const qdc::cx*>(fwd),
+                           reinterpret_cast<qdc::cx*>(bwd), plan, (uint32_t)n, weight,
+                           accumulate != 0);
+}
+
+// host only: no context, no device
+__attribute__((visibility("default"))) size_t qdc_pauli_plan(
+    const unsigned long long* xmask, const unsigned long long* zmask, size_t terms, size_t n,
+    unsigned* out, unsigned long long* group_x, size_t cap) {
+  qdc::PauliPlan plan;
+  if (!out || n > 40 || qdc::pauli_plan(xmask, zmask, nullptr, terms, n, plan)) return SIZE_MAX;
+  const size_t ng = plan.win_x.size() + plan.far_x.size();
+  if (ng > cap || (ng > 0 && !group_x)) return SIZE_MAX;
+  const unsigned v[6] = {qdc::PAULI_W, (unsigned)plan.merged, (unsigned)plan.win_x.size(),
+                         (unsigned)plan.far_x.size(), (unsigned)plan.launches(),
+                         (unsigned)plan.launches()};
+  for (int i = 0; i < 6; ++i) out[i] = v[i];
+  size_t w = 0;
+  for (uint64_t x : plan.win_x) group_x[w++] = x;
+  for (uint64_t x : plan.far_x) group_x[w++] = x;
+  return ng;
 }
 
 __attribute__((visibility("default"))) const char* qdc_abi_sync(void) {

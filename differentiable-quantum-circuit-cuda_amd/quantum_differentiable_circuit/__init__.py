@@ -23,9 +23,11 @@ import numpy as np
 from .common_gates import get_cnot, get_hadamard  # noqa: E402  (common_gates.rs)
 from ._native import (PanicException, KernelStat, PlanOp, check, default_precision, load,
                       ptr, PRECISIONS)
+from .observable import PauliSum
 
 __all__ = ["Circuit", "Circuit32", "Circuit64", "QuantizedTensor", "PanicException",
            "get_q1_grad", "get_q2_grad", "get_q2_grad_diag", "get_qk_grad", "data_transfer",
+           "PauliSum", "pauli_inject",
            "circuit_class",
            "plan", "unpermute", "get_hadamard", "get_cnot"]
 
@@ -738,6 +740,15 @@ class QuantizedTensor:
         check(self._lib.qdc_qkdensity(self._p, ptr(d), arr, k, self.qubits_number))
         return d
 
+    def pauli_energy(self, obs: PauliSum) -> float:
+        """<psi|H|psi> of a Pauli sum (qdc_pauli_energy, include/qdc/pauli.h): real, for a state
+        that need not be normalised; one host sync."""
+        if obs.qubits_number != self.qubits_number:
+            raise PanicException("The observable and the tensor have different sizes.")
+        e = C.c_double(0.0)
+        check(self._lib.qdc_pauli_energy(self._p, *obs._args(), self.qubits_number, C.byref(e)))
+        return float(e.value)
+
     def apply_q2_gate_inv(self, gate, pos2, pos1):
         g = self._gate(gate, 16)
         self._pos2(pos2, pos1)
@@ -808,3 +819,18 @@ def get_qk_grad(fwd, bwd, positions):
     pos = [int(p) for p in positions]
     arr = _qk_positions(pos, fwd.qubits_number)
     return _grad("qdc_qkgrad", fwd, bwd, 1 << (2 * len(pos)), arr, len(pos))
+
+
+def pauli_inject(fwd, bwd, obs: PauliSum, weight=1.0, accumulate=True):
+    """The cotangent of ``fwd.pauli_energy(obs)`` with upstream weight dL/dE (qdc_pauli_inject):
+    bwd += 2 weight conj(H fwd); ``accumulate=False`` overwrites bwd without reading it.  What the
+    density route reaches with conj_and_double, the transposed cotangent as a gate and add."""
+    if fwd.qubits_number != bwd.qubits_number:
+        raise PanicException("fwd and bwd have different lengths.")
+    if obs.qubits_number != fwd.qubits_number:
+        raise PanicException("The observable and the tensor have different sizes.")
+    w = complex(weight)
+    if w.imag != 0.0:
+        raise PanicException("Pauli coefficients must be real.")
+    check(fwd._lib.qdc_pauli_inject(fwd._p, bwd._p, *obs._args(), fwd.qubits_number, w.real,
+                                    1 if accumulate else 0))

@@ -1,7 +1,8 @@
 """ctypes bindings of the HIP hot-path library (libqdc_f32.so / libqdc_f64.so).
 
 The C ABI is declared in ``include/qdc/primitives.h`` (the reference's 18 primitives,
-``src/primitives_bind.rs:15-119``) and ``include/qdc/circuit.h`` (the circuit runtime that
+``src/primitives_bind.rs:15-119``), ``include/qdc/dense.h`` and ``include/qdc/pauli.h`` (their
+extensions) and ``include/qdc/circuit.h`` (the circuit runtime that
 replaces ``src/circuit.rs`` / ``src/quantized_tensor.rs``).  There is no fallback: if the
 library is missing the import fails loudly, and every call that needs a GPU raises the HIP
 error the library reports.
@@ -37,6 +38,7 @@ RUNTIME = (
     "qdc_rq_plan", "qdc_spec_selftest", "qdc_gate_plan", "qdc_lane_plan", "qdc_qkgate", "qdc_qkgrad", "qdc_qkdensity", "qdc_abi_sync", "qdc_abi_profile", "qdc_abi_profile_collect",
     "qdc_jit_stats", "qdc_jit_dir", "qdc_spec_fingerprint", "qdc_spec_selftest_batch",
     "qdc_jit_wait", "qdc_precompile", "qdc_check_schedule", "qdc_trace_program", "qdc_rq_variant",
+    "qdc_pauli_energy", "qdc_pauli_inject", "qdc_pauli_plan",
 )
 
 
@@ -119,6 +121,12 @@ def _proto(lib):
         "qdc_qkgate": (_E, [_P, _P, C.POINTER(C.c_size_t), _S, _S]),
         "qdc_qkgrad": (_E, [_P, _P, _P, C.POINTER(C.c_size_t), _S, _S]),
         "qdc_qkdensity": (_E, [_P, _P, C.POINTER(C.c_size_t), _S, _S]),
+        "qdc_pauli_energy": (_E, [_P, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                  C.POINTER(C.c_double), _S, _S, C.POINTER(C.c_double)]),
+        "qdc_pauli_inject": (_E, [_P, _P, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                  C.POINTER(C.c_double), _S, _S, C.c_double, C.c_int]),
+        "qdc_pauli_plan": (_S, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _S, _S,
+                                C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong), _S]),
         "qdc_abi_sync": (_E, []),
         "qdc_abi_profile": (_E, [C.c_int]),
         "qdc_abi_profile_collect": (_S, [C.POINTER(KernelStat), _S]),

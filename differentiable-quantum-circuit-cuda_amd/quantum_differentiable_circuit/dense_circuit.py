@@ -9,8 +9,13 @@ in place of the q1 / q2 ones:
   uncompute), then, once a cotangent has been injected, ``get_qk_grad(fwd, bwd, positions)`` for
   a variable gate and ``apply_qk_gate_tr`` on bwd; per differentiable density:
   ``conj_and_double`` into a new state, ``apply_qk_gate_tr(cotangent)`` on it, then ``add`` into
-  bwd (the first one becomes bwd).  Variable gates met before the first cotangent get zero
-  gradients.
+  bwd (the first one becomes bwd); per differentiable observable (a ``PauliSum``, its cotangent
+  a real weight dL/dE): one ``pauli_inject(fwd, bwd, obs, weight)``, with ``accumulate=False``
+  into a newly allocated bwd when it is the first cotangent, ``accumulate=True`` otherwise.
+  Variable gates met before the first cotangent get zero gradients.
+
+An observable's forward value is ``state.pauli_energy(obs)``, a Python float, at its place in
+instruction order among the densities.
 
 Gates are 1-D arrays of 4^k values (2^k x 2^k row-major, local index bit (k-1-b) = qubit
 positions[b]); densities come back as (2^k, 2^k) arrays and gradients as 1-D arrays in forward
@@ -29,10 +34,11 @@ from typing import List
 
 import numpy as np
 
-from . import PanicException, QuantizedTensor, data_transfer, get_qk_grad
+from . import (PanicException, PauliSum, QuantizedTensor, data_transfer, get_qk_grad,
+               pauli_inject)
 from .abi_circuit import _slice
 
-CONST_GATE, VAR_GATE, DENSITY, DIFF_DENSITY = range(4)
+CONST_GATE, VAR_GATE, DENSITY, DIFF_DENSITY, OBSERVABLE, DIFF_OBSERVABLE = range(6)
 
 
 class DenseCircuit:
@@ -62,6 +68,18 @@ class DenseCircuit:
     def get_dens_op(self, positions): self._push(DENSITY, positions)
     def get_dens_op_with_grad(self, positions): self._push(DIFF_DENSITY, positions)
 
+    def _push_observable(self, kind, obs):
+        if not isinstance(obs, PauliSum):
+            raise TypeError("argument 'obs': expected a PauliSum")
+        if obs.qubits_number != self.state.qubits_number:
+            raise PanicException("The observable and the tensor have different sizes.")
+        if len(obs) == 0:
+            raise PanicException("The observable has no terms.")
+        self.instructions.append((kind, obs))
+
+    def get_observable_op(self, obs): self._push_observable(OBSERVABLE, obs)
+    def get_observable_op_with_grad(self, obs): self._push_observable(DIFF_OBSERVABLE, obs)
+
     # --- forward --------------------------------------------------------------------------
     def _forward(self, const_gates, var_gates, all_densities) -> List[np.ndarray]:
         if not self.instructions:
@@ -77,6 +95,9 @@ class DenseCircuit:
                     word = "constant" if kind == CONST_GATE else "variable"
                     raise PanicException(f"The number of {word} gates is less than required.")
                 s.apply_qk_gate(_slice(pool.popleft()), pos)
+            elif kind in (OBSERVABLE, DIFF_OBSERVABLE):
+                if kind == DIFF_OBSERVABLE or all_densities:
+                    out.append(s.pauli_energy(pos))
             elif kind == DIFF_DENSITY or all_densities:
                 c = 1 << len(pos)
                 out.append(s.get_qk_density(pos).reshape(c, c))
@@ -87,17 +108,19 @@ class DenseCircuit:
         return out
 
     def run(self, const_gates, var_gates):
-        """Every density matrix, in instruction order."""
+        """Every density matrix and every observable's energy, in instruction order."""
         return self._forward(const_gates, var_gates, True)
 
     def forward(self, const_gates, var_gates):
-        """The differentiable density matrices, in instruction order."""
+        """The differentiable density matrices and energies, in instruction order."""
         return self._forward(const_gates, var_gates, False)
 
     # --- backward -------------------------------------------------------------------------
     def backward(self, grads_wrt_density, const_gates, var_gates) -> List[np.ndarray]:
         """Gradients of the variable gates, forward order; call after ``forward`` with the same
-        gates.  Leaves the forward state uncomputed back to the initial state."""
+        gates.  ``grads_wrt_density`` holds, in the order of ``forward``'s outputs, a cotangent
+        matrix per differentiable density and a real weight per differentiable observable.
+        Leaves the forward state uncomputed back to the initial state."""
         if not self.instructions:
             raise PanicException("The circuit is empty.")
         dens, cg, vg = list(grads_wrt_density), list(const_gates), list(var_gates)
@@ -129,6 +152,18 @@ class DenseCircuit:
                 else:
                     bwd.add(addition)
                     del addition
+            elif kind == DIFF_OBSERVABLE:
+                if not dens:
+                    raise PanicException(
+                        "The number of gradients wrt density matrices is less than required.")
+                w = complex(np.asarray(dens.pop()).reshape(()))
+                if w.imag != 0.0:
+                    raise PanicException("Pauli coefficients must be real.")
+                if bwd is None:
+                    bwd = QuantizedTensor(fwd.qubits_number, fwd._precision)
+                    pauli_inject(fwd, bwd, pos, w.real, accumulate=False)
+                else:
+                    pauli_inject(fwd, bwd, pos, w.real, accumulate=True)
         if cg:
             raise PanicException("Number of constant gates is more than required.")
         if vg:  # circuit.rs:426 words it this way

@@ -1,0 +1,179 @@
+"""Pauli-sum observables: ``H = sum_t c_t P_t`` with real ``c_t`` and Pauli strings ``P_t``.
+
+A ``PauliSum`` holds the terms as the masks of ``include/qdc/pauli.h``: bit q of ``xmask`` means
+X or Y on qubit q, bit q of ``zmask`` means Z or Y (both: Y = [[0, -i], [i, 0]], neither: the
+identity); qubit 0 is the least significant bit of an amplitude's index.  With
+``nY = popcount(x & z)`` and ``j = i ^ x``::
+
+    (P psi)[i] = i^nY * (-1)^popcount(j & z) * psi[j]
+
+``QuantizedTensor.pauli_energy(obs)`` returns ``<psi|H|psi>`` and ``pauli_inject(fwd, bwd, obs,
+weight)`` its cotangent ``bwd (+)= 2 weight conj(H fwd)``, each in one pass over the state for
+every group of terms that fits a tile plus one pass per far-reaching X/Y footprint
+(``csrc/qdc_pauli.hpp``); ``DenseCircuit.get_observable_op[_with_grad]`` puts both into a
+differentiable circuit.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import re
+
+import numpy as np
+
+from ._native import PanicException
+
+_OP = re.compile(r"^([XYZxyz])(\d+)$")
+
+
+def _parse_ops(ops):
+    """``"X0 Y3 Z12"`` or a sequence of ``(qubit, "X"|"Y"|"Z")`` -> [(qubit, letter)]."""
+    if isinstance(ops, str):
+        out = []
+        for tok in ops.split():
+            m = _OP.match(tok)
+            if not m:
+                raise ValueError(f"cannot read the Pauli operator {tok!r} (expected e.g. 'X0 Y3 Z12')")
+            out.append((int(m.group(2)), m.group(1).upper()))
+        return out
+    out = []
+    for q, p in ops:
+        p = str(p).upper()
+        if p not in ("X", "Y", "Z"):
+            raise ValueError(f"a Pauli operator is 'X', 'Y' or 'Z', got {p!r}")
+        out.append((int(q), p))
+    return out
+
+
+def _real_coeff(c):
+    c = complex(c)
+    if c.imag != 0.0:
+        raise PanicException("Pauli coefficients must be real.")
+    if not np.isfinite(c.real):
+        raise PanicException("Pauli coefficients must be finite.")
+    return c.real
+
+
+class PauliSum:
+    """``PauliSum(qubits_number, [(coeff, ops), ...])``: ``ops`` is a string such as
+    ``"X0 Y3 Z12"`` (``""`` is the identity) or a sequence of ``(qubit, "X"|"Y"|"Z")``.  Terms
+    with the same string merge (their coefficients add); the terms are kept sorted by
+    ``(xmask, zmask)``."""
+
+    def __init__(self, qubits_number: int, terms):
+        n = int(qubits_number)
+        merged = {}
+        for coeff, ops in terms:
+            c = _real_coeff(coeff)
+            x = z = 0
+            for q, p in _parse_ops(ops):
+                if q < 0 or q >= n:
+                    raise PanicException("pos is out of the bound.")
+                bit = 1 << q
+                if (x | z) & bit:
+                    raise PanicException("a qubit appears twice in a Pauli term.")
+                if p in ("X", "Y"):
+                    x |= bit
+                if p in ("Z", "Y"):
+                    z |= bit
+            merged[(x, z)] = merged.get((x, z), 0.0) + c
+        self._set(n, merged)
+
+    @classmethod
+    def from_masks(cls, qubits_number, coeffs, xmasks, zmasks):
+        n = int(qubits_number)
+        coeffs, xmasks, zmasks = list(coeffs), list(xmasks), list(zmasks)
+        if not len(coeffs) == len(xmasks) == len(zmasks):
+            raise ValueError("coeffs, xmasks and zmasks must have one entry per term")
+        merged = {}
+        for c, x, z in zip(coeffs, xmasks, zmasks):
+            x, z = int(x), int(z)
+            if x < 0 or z < 0 or (x | z) >> n:
+                raise PanicException("pos is out of the bound.")
+            merged[(x, z)] = merged.get((x, z), 0.0) + _real_coeff(c)
+        self = cls.__new__(cls)
+        self._set(n, merged)
+        return self
+
+    def _set(self, n, merged):
+        if n < 0 or n > 40:
+            raise PanicException(f"qubits_number {n} is out of the supported range (<= 40).")
+        keys = sorted(merged)
+        self.qubits_number = n
+        self.xmasks = np.array([k[0] for k in keys], dtype=np.uint64)
+        self.zmasks = np.array([k[1] for k in keys], dtype=np.uint64)
+        self.coeffs = np.array([merged[k] for k in keys], dtype=np.float64)
+
+    def __len__(self):
+        return int(self.coeffs.size)
+
+    def terms(self):
+        """[(coeff, xmask, zmask)], sorted by (xmask, zmask)."""
+        return [(float(c), int(x), int(z)) for c, x, z in zip(self.coeffs, self.xmasks, self.zmasks)]
+
+    def _args(self):
+        """(xmask*, zmask*, coeff*, terms) of the C entry points (the arrays stay owned here)."""
+        ull = C.POINTER(C.c_ulonglong)
+        return (self.xmasks.ctypes.data_as(ull), self.zmasks.ctypes.data_as(ull),
+                self.coeffs.ctypes.data_as(C.POINTER(C.c_double)), len(self))
+
+    def apply(self, psi):
+        """``H psi`` on the host in complex128, by the index rule of the definition."""
+        psi = np.asarray(psi, dtype=np.complex128).reshape(-1)
+        if psi.size != 1 << self.qubits_number:
+            raise PanicException("Size of the given state does not match the size of the tensor.")
+        idx = np.arange(psi.size, dtype=np.uint64)
+        out = np.zeros_like(psi)
+        for c, x, z in self.terms():
+            j = idx ^ np.uint64(x)
+            sign = 1.0 - 2.0 * (_popcount(j & np.uint64(z)) & 1)
+            out += (c * 1j ** (bin(x & z).count("1") % 4)) * sign * psi[j]
+        return out
+
+    def to_matrix(self):
+        """The dense 2^n x 2^n matrix (complex128), n <= 12."""
+        n = self.qubits_number
+        if n > 12:
+            raise PanicException("to_matrix() is for at most 12 qubits.")
+        dim = 1 << n
+        idx = np.arange(dim, dtype=np.uint64)
+        m = np.zeros((dim, dim), dtype=np.complex128)
+        for c, x, z in self.terms():
+            j = idx ^ np.uint64(x)
+            sign = 1.0 - 2.0 * (_popcount(j & np.uint64(z)) & 1)
+            m[idx, j] += (c * 1j ** (bin(x & z).count("1") % 4)) * sign
+        return m
+
+
+def _popcount(a):
+    a = a.astype(np.uint64)
+    count = np.zeros(a.shape, dtype=np.int64)
+    while a.any():
+        count += (a & np.uint64(1)).astype(np.int64)
+        a = a >> np.uint64(1)
+    return count
+
+
+def plan(obs: PauliSum, precision=None):
+    """The launch plan of ``pauli_energy`` / ``pauli_inject`` (qdc_pauli_plan, host only):
+    ``{"W", "merged", "window_groups", "far_groups", "energy_launches", "inject_launches",
+    "group_x"}``."""
+    return plan_masks(obs.qubits_number, obs.xmasks, obs.zmasks, precision)
+
+
+def plan_masks(qubits_number, xmasks, zmasks, precision=None):
+    """``plan`` on raw masks (duplicates allowed); None where the library rejects them."""
+    from ._native import default_precision, load
+    lib = load(precision or default_precision())
+    xs = np.ascontiguousarray(xmasks, dtype=np.uint64)
+    zs = np.ascontiguousarray(zmasks, dtype=np.uint64)
+    ull = C.POINTER(C.c_ulonglong)
+    out = (C.c_uint * 6)()
+    cap = max(1, xs.size)
+    gx = (C.c_ulonglong * cap)()
+    k = lib.qdc_pauli_plan(xs.ctypes.data_as(ull), zs.ctypes.data_as(ull), xs.size,
+                           int(qubits_number), out, gx, cap)
+    if k == C.c_size_t(-1).value:
+        return None
+    return {"W": out[0], "merged": out[1], "window_groups": out[2], "far_groups": out[3],
+            "energy_launches": out[4], "inject_launches": out[5],
+            "group_x": [int(gx[i]) for i in range(k)]}
