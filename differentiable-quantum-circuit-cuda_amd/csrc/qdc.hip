@@ -556,7 +556,7 @@ static const char* spec_program_for(unsigned tile_bits, const unsigned* kinds, c
   if (tile_bits == t2bits && force_one) knobs.rq_wave |= pf ? 2 | 8 : 2;
   const qdc::RqVariant* V = qdc::rq_select(two, tile_bits, knobs, false);
   if (!V || !V->prefix) return "tile_bits: not a specialized pass's tile";
-  const bool keep = spec_half && V->ns == 5;  // (build_program's planning)
+  const bool keep = spec_half && V->ns == 5;  // (emit_rq_pass's planning)
   const qdc::RqPlan plan = qdc::rq_plan(st, tile_bits, nullptr, true, V->ns, keep);
   std::vector<qdc::SpecStep> sst;
   qdc::RqLayout cur = plan.load;
@@ -575,7 +575,7 @@ static const char* spec_program_for(unsigned tile_bits, const unsigned* kinds, c
       F.t1 = (s.cs & 7u) * 8u + (s.cs >> 3);  // the runtime's canonical S1 < S2
     sst.push_back(qdc::SpecStep{false, cur, cur, F});
   }
-  // (build_program's choice: a program whose relayouts all keep a slot runs on half buffers
+  // (spec_entry's choice: a program whose relayouts all keep a slot runs on half buffers
   // where its variant has that form)
   const bool half = V->pass_half && spec_half && !qdc::spec_imm() && qdc::spec_half_ok(sst);
   const qdc::SpecKind K = qdc::spec_kind(*V, half);
@@ -622,6 +622,29 @@ QDC_API const char* qdc_spec_selftest_batch(unsigned tile_bits, const size_t* co
   return nullptr;
 }
 
+// host-only hooks (qdc_trace_program, qdc_check_schedule): an instruction's kind and positions
+// as qdc_circuit_push accepts them (positions < n, a two-qubit op's two positions distinct)
+// (qdc_precompile checks the kind only: its calls' own validation reports the positions)
+static const char* check_instr(int kind, unsigned p2, unsigned p1, size_t n, size_t i,
+                               bool positions) {
+  if (kind < QDC_CONST_Q2 || kind > QDC_DIFF_Q1_DENSITY)
+    return qdc::fail("unknown instruction kind %d", kind);
+  const bool q1 = qdc::is_q1_gate(kind) || qdc::is_q1_density(kind);
+  if (positions && (p2 >= n || (!q1 && (p1 >= n || p1 == p2))))
+    return qdc::fail("instruction %zu: invalid positions (%u, %u) on %zu qubits", i, p2, p1, n);
+  return nullptr;
+}
+// the checked instructions of a dry circuit, as qdc_circuit_push stores them
+static const char* push_dry(qdc::Circuit& k, const int* kinds, const unsigned* pos2,
+                            const unsigned* pos1, size_t count, bool positions) {
+  for (size_t i = 0; i < count; ++i) {
+    QDC_TRY(check_instr(kinds[i], pos2[i], pos1[i], k.n, i, positions));
+    const bool q1 = qdc::is_q1_gate(kinds[i]) || qdc::is_q1_density(kinds[i]);
+    k.ins.push_back({kinds[i], pos2[i], q1 ? 0u : pos1[i]});
+  }
+  return nullptr;
+}
+
 // Ahead-of-time compilation of a circuit's specialized passes (build time, no GPU): a host-only
 // dry run of forward(cg, vg) then backward(dg, cg, vg) on `world` shards builds the same pass
 // programs as the runtime's calls, and every specialized kernel they would launch is compiled
@@ -634,13 +657,7 @@ QDC_API const char* qdc_precompile(size_t n, int world, const int* kinds, const 
   if (n == 0 || n > 40 || world < 1) return qdc::fail("invalid precompile arguments");
   qdc::Circuit k;
   QDC_TRY(k.init_dry((uint32_t)n, world));
-  for (size_t i = 0; i < count; ++i) {
-    const int kind = kinds[i];
-    if (kind < QDC_CONST_Q2 || kind > QDC_DIFF_Q1_DENSITY)
-      return qdc::fail("unknown instruction kind %d", kind);
-    const bool q1 = qdc::is_q1_gate(kind) || qdc::is_q1_density(kind);
-    k.ins.push_back({kind, pos2[i], q1 ? 0u : pos1[i]});
-  }
+  QDC_TRY(push_dry(k, kinds, pos2, pos1, count, false));  // (positions: validate_forward)
   qdc::Flat cf(cg, cl, nc), vf(vg, vl, nv), df(dg, dl, nd);
   std::vector<qdc_complex> dens(std::max<size_t>(k.output_size(QDC_MODE_FORWARD), 1));
   QDC_TRY(k.execute(QDC_MODE_FORWARD, cf, vf, dens.data()));
@@ -672,17 +689,6 @@ QDC_API const char* qdc_precompile(size_t n, int world, const int* kinds, const 
   return qdc::SpecJit::get().compile_only(names, srcs);
 }
 
-// host-only hooks (qdc_trace_program, qdc_check_schedule): an instruction's kind and positions
-// as qdc_circuit_push accepts them (positions < n, a two-qubit op's two positions distinct)
-static const char* check_instr(int kind, unsigned p2, unsigned p1, size_t n, size_t i) {
-  if (kind < QDC_CONST_Q2 || kind > QDC_DIFF_Q1_DENSITY)
-    return qdc::fail("unknown instruction kind %d", kind);
-  const bool q1 = qdc::is_q1_gate(kind) || qdc::is_q1_density(kind);
-  if (p2 >= n || (!q1 && (p1 >= n || p1 == p2)))
-    return qdc::fail("instruction %zu: invalid positions (%u, %u) on %zu qubits", i, p2, p1, n);
-  return nullptr;
-}
-
 QDC_API const char* qdc_trace_program(size_t n, int world, const int* kinds, const unsigned* pos2,
                                       const unsigned* pos1, size_t count, const qdc_complex* cg,
                                       const size_t* cl, size_t nc, const qdc_complex* vg,
@@ -694,12 +700,7 @@ QDC_API const char* qdc_trace_program(size_t n, int world, const int* kinds, con
     return qdc::fail("invalid trace arguments");
   qdc::Circuit k;
   QDC_TRY(k.init_dry((uint32_t)n, world));
-  for (size_t i = 0; i < count; ++i) {
-    const int kind = kinds[i];
-    if (const char* e = check_instr(kind, pos2[i], pos1[i], n, i)) return e;
-    const bool q1 = qdc::is_q1_gate(kind) || qdc::is_q1_density(kind);
-    k.ins.push_back({kind, pos2[i], q1 ? 0u : pos1[i]});
-  }
+  QDC_TRY(push_dry(k, kinds, pos2, pos1, count, true));
   k.tracing = true;
   qdc::Flat cf(cg, cl, nc), vf(vg, vl, nv), df(dg, dl, nd);
   std::vector<qdc_complex> dens(std::max<size_t>(k.output_size(QDC_MODE_FORWARD), 1));
@@ -724,11 +725,7 @@ QDC_API const char* qdc_check_schedule(size_t n, int world, const int* kinds, co
     return qdc::fail("invalid schedule arguments");
   qdc::Circuit k;
   QDC_TRY(k.init_dry((uint32_t)n, world));
-  for (size_t i = 0; i < count; ++i) {
-    if (const char* e = check_instr(kinds[i], pos2[i], pos1[i], n, i)) return e;
-    const bool q1 = qdc::is_q1_gate(kinds[i]) || qdc::is_q1_density(kinds[i]);
-    k.ins.push_back({kinds[i], pos2[i], q1 ? 0u : pos1[i]});
-  }
+  QDC_TRY(push_dry(k, kinds, pos2, pos1, count, true));
   k.inexact.assign(k.ins.size(), 0);
   std::vector<qdc_plan_op> pl = k.plan(QDC_MODE_FORWARD);
   k.sched_mirror = true;

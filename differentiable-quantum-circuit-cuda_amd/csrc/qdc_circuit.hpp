@@ -38,8 +38,22 @@ struct Flat {
     }
   }
   size_t size() const { return len.size(); }
+  size_t total() const { return len.empty() ? 0 : off.back() + len.back(); }  // values in all
   const qdc_complex* at(size_t i) const { return data + off[i]; }
 };
+
+// a physical position after a pass's swaps, applied in order (qdc_fusion.hpp FusionItem::swaps)
+inline uint32_t apply_swaps(const std::vector<std::pair<uint32_t, uint32_t>>& swaps, uint32_t p) {
+  for (const auto& sw : swaps) {
+    if (p == sw.first) p = sw.second;
+    else if (p == sw.second) p = sw.first;
+  }
+  return p;
+}
+// the applied matrix and the pull-back of a gate of this kind (qdc_device.hpp GateMats)
+inline const char* gate_mats(int kind, const qdc_complex* g, bool uncompute, GateMats& m) {
+  return gate_mats(g, is_diag(kind), is_q1_gate(kind), is_nonu(kind), uncompute, m);
+}
 
 // The assertion sequence of QuantizedTensor::apply_* (quantized_tensor.rs:100-152).
 inline const char* check_gate(const Instr& in, size_t len, uint32_t n) {
@@ -264,7 +278,7 @@ struct Circuit {
   // compiler contracts the scalar complex arithmetic differently), so a deep f64 program stays
   // generic — reproducible from call to call — unless QDC_SPEC_ASYNC=1 opts in
   int spec_async = sizeof(real) == 4 ? 1 : 0;
-  // generated kernels by pass program (key: qdc_circuit build_program), with their functions
+  // generated kernels by pass program (key: spec_entry), with their functions
   std::map<std::vector<uint32_t>, SpecEntry> spec_cache;
   uint64_t spec_epoch = 0;
   int rq_permute = 1;      // gate-only passes permute their tile's qubits (QDC_RQ_PERM)
@@ -306,7 +320,7 @@ struct Circuit {
     return mirror && fuse && fuse_max_ops >= 2 && use_rq && (sizeof(real) == 4 || rq64);
   }
   // The kernel variant (qdc_variant.hpp) of a register-resident pass on 2^tbits-amplitude tiles:
-  // the one selection that planning (build_program), specialization and launch (launch_rq) share
+  // the one selection that planning (emit_rq_pass), specialization and launch (launch_rq) share
   const char* rq_variant(bool two, uint32_t tbits, const RqVariant*& V) const {
     V = rq_select(two, tbits, rqk, mirror_on());
     if (!V)
@@ -609,18 +623,25 @@ struct Circuit {
     return nullptr;
   }
 
-  size_t output_count(int mode) const {
-    size_t c = 0;
-    for (auto& in : ins)
-      if (is_diff_density(in.kind) || (mode == QDC_MODE_RUN && is_density(in.kind))) ++c;
-    return c;
+  // the densities a call of this mode returns
+  static bool is_output(int kind, int mode) {
+    return is_diff_density(kind) || (mode == QDC_MODE_RUN && is_density(kind));
   }
   size_t output_size(int mode) const {
     size_t c = 0;
     for (auto& in : ins)
-      if (is_diff_density(in.kind) || (mode == QDC_MODE_RUN && is_density(in.kind)))
-        c += is_q1_density(in.kind) ? 4 : 16;
+      if (is_output(in.kind, mode)) c += is_q1_density(in.kind) ? 4 : 16;
     return c;
+  }
+  // the output index of every instruction that has one, and the outputs' widths in order
+  void outputs(int mode, std::vector<uint32_t>& out_idx, std::vector<int>& widths) const {
+    out_idx.assign(ins.size(), 0);
+    widths.clear();
+    for (size_t k = 0; k < ins.size(); ++k)
+      if (is_output(ins[k].kind, mode)) {
+        out_idx[k] = (uint32_t)widths.size();
+        widths.push_back(is_q1_density(ins[k].kind) ? 4 : 16);
+      }
   }
   size_t n_var() const {
     size_t c = 0;
@@ -796,8 +817,23 @@ struct Circuit {
     std::vector<qdc_complex> cgates, vgates;
     std::vector<uint8_t> inexact;
     std::vector<uint32_t> end_phys;  // the layout the forward left
+    void capture(const Flat& cg, const Flat& vg, const std::vector<qdc_plan_op>& pl,
+                 const std::vector<Item>& its, std::vector<std::vector<SMat>>&& mats,
+                 const std::vector<uint8_t>& inex) {
+      plan = pl;
+      items = its;
+      stage_mats = std::move(mats);
+      cgates.assign(cg.data, cg.data + cg.total());
+      vgates.assign(vg.data, vg.data + vg.total());
+      inexact = inex;
+    }
+    static bool same(const Flat& f, const std::vector<qdc_complex>& v) {
+      const size_t nf = f.total();
+      return nf == v.size() && (nf == 0 || std::memcmp(f.data, v.data(), nf * sizeof(qdc_complex)) == 0);
+    }
+    bool same_gates(const Flat& cg, const Flat& vg) const { return same(cg, cgates) && same(vg, vgates); }
   } mrec;
-  std::vector<std::vector<SMat>>* rec_mats = nullptr;  // build_program records stage matrices here
+  std::vector<std::vector<SMat>>* rec_mats = nullptr;  // gate_stage records stage matrices here
   // The backward schedule as the forward's passes run in reverse (mirror mode): op positions
   // mapped into the layout each reverse pass starts from (the forward pass's store layout),
   // stages and the ops in them reversed, the forward's swaps undone in reverse order.
@@ -809,18 +845,11 @@ struct Circuit {
     for (size_t k = F.size(); k-- > 0;) {
       const Item& f = F[k];
       if (f.type != 0 && f.type != 1 && f.type != 2) return false;
-      auto sigma = [&](uint32_t p) {
-        for (const auto& sw : f.swaps) {
-          if (p == sw.first) p = sw.second;
-          else if (p == sw.second) p = sw.first;
-        }
-        return p;
-      };
       auto push = [&](uint32_t fi) {
         qdc_plan_op op = mrec.plan[fi];
         if (op.type == QDC_PLAN_OP) {
-          op.pos2 = sigma(op.pos2);
-          op.pos1 = sigma(op.pos1);
+          op.pos2 = apply_swaps(f.swaps, op.pos2);
+          op.pos1 = apply_swaps(f.swaps, op.pos1);
         }
         pl.push_back(op);
         return (uint32_t)(pl.size() - 1);
@@ -878,13 +907,15 @@ struct Circuit {
       }
       items.push_back(std::move(b));
     }
-    first_inject = pl.size();
-    for (size_t i = 0; i < pl.size(); ++i)
-      if (pl[i].type == QDC_PLAN_OP && is_diff_density(ins[pl[i].instr].kind)) {
-        first_inject = i;
-        break;
-      }
+    first_inject = first_injection(pl);
     return true;
+  }
+  // plan index of the first cotangent injection (the ops before it only uncompute fwd), or the
+  // plan's size
+  size_t first_injection(const std::vector<qdc_plan_op>& pl) const {
+    for (size_t i = 0; i < pl.size(); ++i)
+      if (pl[i].type == QDC_PLAN_OP && is_diff_density(ins[pl[i].instr].kind)) return i;
+    return pl.size();
   }
   static constexpr uint32_t TILE_CHUNKS_1 = FusionPlanner::TILE_CHUNKS_1;
   static constexpr uint32_t TILE_CHUNKS_2 = FusionPlanner::TILE_CHUNKS_2;
@@ -911,7 +942,7 @@ struct Circuit {
     for (FusionItem& f : planner().fuse_items(plan, backward, first_inject)) {
       Item it;
       static_cast<FusionItem&>(it) = std::move(f);
-      if (it.type == 2) it.stages = stage_partition(it.ops, plan, backward);
+      if (it.type == 2) it.stages = planner().stage_partition(it.ops, plan, backward);
       items.push_back(std::move(it));
     }
     return items;
@@ -980,11 +1011,6 @@ struct Circuit {
     if (rq_plan_cache.size() >= 8192) rq_plan_cache.clear();
     return rq_plan_cache.emplace(std::move(key), rq_plan(rs, tbits, src, maxcl, ns, keep)).first->second;
   }
-  std::vector<std::vector<uint32_t>> stage_partition(const std::vector<uint32_t>& pass,
-                                                     const std::vector<qdc_plan_op>& plan,
-                                                     bool backward) const {
-    return planner().stage_partition(pass, plan, backward);
-  }
   // per call: which gates are not unitary to working precision (qdc_fusion.hpp)
   void mark_inexact(const Flat& cg, const Flat& vg, const std::vector<size_t>& gidx) {
     inexact.assign(ins.size(), 0);
@@ -1019,6 +1045,37 @@ struct Circuit {
       }
     return e;
   }
+  // --- the pass program: build_program and its steps --------------------------------------------
+  // One stage op of the pass being built: the op as the LDS kernel takes it, its qubits (a mask
+  // of physical positions), its order classes (qdc_fusion.hpp) and its reduction slot (Gamma
+  // stages), else -1
+  struct StageOp {
+    fop F;
+    uint64_t q;
+    uint32_t cls;
+    int slot;
+  };
+  // One build_program call: its inputs, the write cursors of the program (fo fops and mo matrix
+  // values so far, the next Gamma slot) and the per-pass scratch, reserved once and reused
+  struct Build {
+    const std::vector<qdc_plan_op>& plan;
+    bool backward;
+    size_t first_inject;
+    const Flat &cg, &vg;
+    const std::vector<size_t>& gidx;
+    const std::vector<uint32_t>& var_idx;
+    const std::vector<uint32_t>& out_idx;
+    const Flat* dg;
+    fop* fops;
+    cx* mats;
+    size_t fo, mo;
+    uint32_t next_slot;
+    std::vector<StageOp> ops;        // the pass's stage ops in program order
+    std::vector<StageGateIn> gates;  // the gates of the stage being composed
+    std::vector<RqStage> rs;
+    std::vector<SpecStep> sst;
+    std::vector<uint32_t> key;
+  };
   // Lay out every fused pass's stage descriptors and stage matrices (A = product of the
   // applied matrices, B = product of the bwd pull-backs) in one pinned buffer, then upload it.
   // backward: `first_inject` = plan index of the first cotangent injection (passes before it
@@ -1034,17 +1091,52 @@ struct Circuit {
     stage_post.clear();
     if (spec_cache.size() >= 4096 && !dry) spec_cache.clear();  // bounded; items of this call point into it
     size_t nops = 0;
-    for (size_t ii = 0; ii < items.size(); ++ii)
-      if (items[ii].type == 2) nops += items[ii].stages.size();
+    for (const Item& it : items)
+      if (it.type == 2) nops += it.stages.size();
     if (nops == 0) return nullptr;
+    QDC_TRY(reserve_program(nops, items.size(), mats_off));
+    Build B{plan, backward, first_inject, cg, vg, gidx, var_idx, out_idx, dg,
+            reinterpret_cast<fop*>(prog_host), reinterpret_cast<cx*>(prog_host + mats_off), 0, 0,
+            nvar, {}, {}, {}, {}, {}};
+    B.ops.reserve(fuse_max_ops);
+    B.gates.reserve(fuse_max_ops);
+    B.rs.reserve(fuse_max_ops);
+    B.sst.reserve(2 * (size_t)fuse_max_ops + 1);
+    for (size_t ii = 0; ii < items.size(); ++ii) {
+      Item& it = items[ii];
+      if (it.type != 2) continue;
+      const bool two = backward && it.ops[0] >= first_inject;
+      QDC_TRY(build_stages(B, it, ii, two));
+      QDC_TRY(classify_pass(B, it, two));
+      if (it.rq)
+        QDC_TRY(emit_rq_pass(B, it, two));
+      else
+        emit_lds_pass(B, it);
+    }
+    if (dry) {  // the kernels this call would compile / load
+      for (Item& it : items)
+        if (it.spec && std::find(dry_specs.begin(), dry_specs.end(), it.spec) == dry_specs.end())
+          dry_specs.push_back(it.spec);
+      return nullptr;
+    }
+    for (auto& d : devs) {  // prog_host is not rewritten before the call's final sync
+      QDC_TRY(d->ctx.use());
+      QDC_HIP(hipMemcpyAsync(d->prog_dev, prog_host, mats_off + B.mo * sizeof(cx),
+                             hipMemcpyHostToDevice, d->ctx.stream));
+    }
+    return spec_load(items);
+  }
+  // Step 1: size the program of nops stages in nitems items and, where it outgrew them,
+  // reallocate the pinned staging buffer and every device's copy (a dry run: dry_prog)
+  const char* reserve_program(size_t nops, size_t nitems, size_t& mats_off) {
     // register-resident passes add relayout ops (<= one per stage, plus the return to L0) and
     // 12-cx layout descriptors (one per relayout, plus L0)
-    const size_t nfops = 2 * nops + items.size();
+    const size_t nfops = 2 * nops + nitems;
     mats_off = ((nfops * sizeof(fop) + 255) / 256) * 256;
     // matrices <= 2 R^2 = 32 per stage; layouts <= 12 cx; one rqio per register-resident pass
     const size_t bytes =
         mats_off + (nops * 32 + nfops * (sizeof(rq_layout) / sizeof(cx)) +
-                    items.size() * (sizeof(rqio) / sizeof(cx))) *
+                    nitems * (sizeof(rqio) / sizeof(cx))) *
                        sizeof(cx);
     if (dry && bytes > prog_cap) {
       dry_prog.resize(bytes);
@@ -1064,404 +1156,324 @@ struct Circuit {
       QDC_HIP(hipHostMalloc(&prog_host, bytes));
       prog_cap = bytes;
     }
-    fop* fops = reinterpret_cast<fop*>(prog_host);
-    cx* mats = reinterpret_cast<cx*>(prog_host + mats_off);
-    size_t fo = 0, mo = 0;
-    uint32_t next_slot = nvar;
-    for (size_t ii = 0; ii < items.size(); ++ii) {
-      Item& it = items[ii];
-      if (it.type != 2) continue;
-      it.fop_off = fo * sizeof(fop);
-      it.grad_slots.clear();
-      it.flops_per_amp = 0;
-      const bool two = backward && it.ops[0] >= first_inject;
-      it.has_red = false;
-      it.writes_f = false;
-      std::vector<fop> pf;  // the pass's stage ops in program order
-      std::vector<uint64_t> pq;  // their qubits (physical positions)
-      std::vector<uint32_t> pc;  // their order classes (qdc_fusion.hpp)
-      std::vector<int> pslot;    // their reduction slot (Gamma stages), else -1
-      pf.reserve(it.stages.size());
-      const FusionPlanner PL = planner();
-      for (const auto& st : it.stages) {
-        uint64_t q = 0;
-        uint32_t c = 0;
-        for (uint32_t pi : st) {
-          q |= (1ull << plan[pi].pos2) | (1ull << plan[pi].pos1);
-          c |= PL.op_class(plan[pi], backward);
-        }
-        pq.push_back(q);
-        pc.push_back(c);
-      }
-      auto local_bit = [&](uint32_t p) -> uint32_t {
-        if (p < (uint32_t)LV + it.lc) return p;
-        for (uint32_t r = 0; r < it.h; ++r)
-          if (it.hb[r] == p - LV) return LV + it.lc + r;
-        return 0xffffffffu;  // unreachable: tile_config covered every bit
-      };
-      if (rec_mats) (*rec_mats)[ii].clear();
-      for (size_t sj = 0; sj < it.stages.size(); ++sj) {
-        const auto& st = it.stages[sj];
-        if (rec_mats && is_meas(plan[st[0]])) (*rec_mats)[ii].push_back(smat_identity(2));
-        if (is_meas(plan[st[0]])) {  // density (forward) or cotangent injection (backward)
-          const qdc_plan_op& op = plan[st[0]];
-          const Instr& in = ins[op.instr];
-          const bool q1 = is_q1_density(in.kind);
-          const int R = q1 ? 2 : 4;
-          pf.emplace_back();
-          pslot.push_back(-1);
-          fop& F = pf.back();
-          F.t1 = local_bit(q1 ? op.pos2 : op.pos1);
-          F.t2 = local_bit(op.pos2);
-          F.mat = (uint32_t)mo;
-          for (int i = 0; i < 2 * R * R; ++i) mats[mo + i] = cx{0, 0};
-          if (backward) {  // b += (G^T on pos) (2 conj f), G = conj of the JAX cotangent
-            F.kind = q1 ? FK_INJ1 : FK_INJ2;
-            const qdc_complex* gd = dg->at(gidx[op.instr]);
-            if (q1) {
-              const mat<2> m = transpose<2>(to_mat<2>(gd));
-              for (int i = 0; i < 4; ++i) mats[mo + i] = m.a[i];
-            } else {
-              const mat<4> m = transpose<4>(to_mat<4>(gd));
-              for (int i = 0; i < 16; ++i) mats[mo + i] = m.a[i];
-            }
-            it.flops_per_amp += 8.0 * (q1 ? 2.0 : 4.0);
-          } else {
-            F.kind = q1 ? FK_DENS1 : FK_DENS2;
-            it.grad_slots.push_back(out_idx[op.instr]);
-            it.has_red = true;
-            it.flops_per_amp += 8.0 * (q1 ? 2.0 : 4.0);
-          }
-          mo += 2 * R * R;
-          continue;
-        }
-        // stage qubits (physical positions), lo < hi
-        uint64_t qm = 0;
-        bool all_diag = true, any_grad = false;
-        for (uint32_t pi : st) {
-          qm |= (1ull << plan[pi].pos2) | (1ull << plan[pi].pos1);
-          all_diag = all_diag && is_diag(ins[plan[pi].instr].kind);
-          any_grad = any_grad || (two && is_var(ins[plan[pi].instr].kind));
-        }
-        const uint32_t lo = (uint32_t)__builtin_ctzll(qm);
-        const uint32_t hi = 63u - (uint32_t)__builtin_clzll(qm);
-        const int R = lo == hi ? 2 : 4;
-        SMat A = smat_identity(R);
-        SMatD B = smat_identity<double>(R);
-        StagePost post;
-        post.R = R;
-        post.diag_only = all_diag;
-        for (uint32_t pi : st) {
-          const qdc_plan_op& op = plan[pi];
-          const Instr& in = ins[op.instr];
-          const qdc_complex* g4 = is_const(in.kind) ? cg.at(gidx[op.instr]) : vg.at(gidx[op.instr]);
-          const bool dg = is_diag(in.kind);
-          int role;
-          if (R == 2)
-            role = ROLE_Q1_ONLY;
-          else if (is_q1_gate(in.kind))
-            role = op.pos2 == lo ? ROLE_Q1_LO : ROLE_Q1_HI;
-          else
-            role = op.pos2 == hi ? ROLE_Q2 : ROLE_Q2_SWAP;
-          // the applied matrix a (forward: U; uncompute: U^dagger / U^-1 / conj diagonal) and
-          // the pull-back b = U^T (diagonal: d), each in the gate's own basis
-          cd ga[16];
-          cdd gb[16];
-          if (dg) {
-            const diag4 d = to_diag(g4);
-            const diag4 a = backward ? conj_diag(d) : d;
-            for (int i = 0; i < 4; ++i) {
-              ga[i] = cd(a.a[i].x, a.a[i].y);
-              gb[i] = cdd(d.a[i].x, d.a[i].y);
-            }
-          } else if (is_q1_gate(in.kind)) {
-            const mat<2> u = to_mat<2>(g4);
-            mat<2> a = u;
-            if (backward) {
-              if (is_nonu(in.kind))
-                QDC_TRY(inverse<2>(u, a));
-              else
-                a = conj_transpose<2>(u);
-            }
-            const mat<2> bt = transpose<2>(u);
-            for (int i = 0; i < 4; ++i) {
-              ga[i] = cd(a.a[i].x, a.a[i].y);
-              gb[i] = cdd(bt.a[i].x, bt.a[i].y);
-            }
-          } else {
-            const mat<4> u = to_mat<4>(g4);
-            mat<4> a = u;
-            if (backward) {
-              if (is_nonu(in.kind))
-                QDC_TRY(inverse<4>(u, a));
-              else
-                a = conj_transpose<4>(u);
-            }
-            const mat<4> bt = transpose<4>(u);
-            for (int i = 0; i < 16; ++i) {
-              ga[i] = cd(a.a[i].x, a.a[i].y);
-              gb[i] = cdd(bt.a[i].x, bt.a[i].y);
-            }
-          }
-          const SMat Ea = stage_embed(ga, dg, role, R);
-          const SMatD Eb = stage_embed(gb, dg, role, R);
-          const SMat Anew = smat_mul(Ea, A);
-          if (two && is_var(in.kind))
-            post.gates.push_back(StageGate{var_idx[op.instr], dg, role, B, smat_double(smat_transpose(Anew))});
-          A = Anew;
-          B = smat_mul(Eb, B);
-        }
-        if (rec_mats) (*rec_mats)[ii].push_back(A);  // the forward's matrix, its own frame
-        // a mirrored backward stage uncomputes with exactly the adjoint of the forward's matrix
-        // (same rounding; the forward frame's two qubits may have swapped order under the
-        // forward pass's permutation)
-        SMat Aup = A;
-        bool from_fwd = false;
-        if (backward && !it.mirror_of.empty()) {
-          bool nonu = false;
-          for (uint32_t pi : st) nonu = nonu || is_nonu(ins[plan[pi].instr].kind);
-          const auto& mo_ = it.mirror_of[sj];
-          if (!nonu && mo_.first < mrec.stage_mats.size() && mo_.second < mrec.stage_mats[mo_.first].size()) {
-            const SMat& Pf = mrec.stage_mats[mo_.first][mo_.second];
-            if (Pf.R == R) {
-              // forward lo / hi positions vs this stage's: swapped when the forward's lower
-              // qubit now sits above the other
-              uint32_t flo = 64, fhi = 0;
-              for (uint32_t fi : mrec.items[mo_.first].stages[mo_.second]) {
-                const qdc_plan_op& fo = mrec.plan[fi];
-                flo = std::min({flo, fo.pos2, fo.pos1});
-                fhi = std::max({fhi, fo.pos2, fo.pos1});
-              }
-              const auto& fsw = mrec.items[mo_.first].swaps;
-              auto sig = [&](uint32_t p) {
-                for (const auto& sw : fsw) {
-                  if (p == sw.first) p = sw.second;
-                  else if (p == sw.second) p = sw.first;
-                }
-                return p;
-              };
-              const bool swapped = R == 4 && sig(flo) > sig(fhi);
-              SMat At = Pf;
-              for (int pp = 0; pp < R; ++pp)
-                for (int qq = 0; qq < R; ++qq) {
-                  const int sp = swapped ? swap_bits4(pp) : pp, sq = swapped ? swap_bits4(qq) : qq;
-                  At.a[pp * R + qq] = std::conj(Pf.a[sq * R + sp]);
-                }
-              Aup = At;
-              from_fwd = true;
-            }
-          }
-        }
-        if (tracing) {  // (physical positions; trace_logical maps them to logical qubits)
-          TraceOp t{backward ? 1u : 0u, (uint32_t)ii, hi, lo, (uint32_t)R, all_diag ? 1u : 0u,
-                    from_fwd ? 1u : 0u, 0u, {}};
-          for (int i = 0; i < R * R; ++i) {
-            const bool keep = !all_diag || i % (R + 1) == 0;
-            t.m[i].re = keep ? (qdc_real)(real)Aup.a[i].real() : 0;
-            t.m[i].im = keep ? (qdc_real)(real)Aup.a[i].imag() : 0;
-          }
-          trace.push_back(t);
-        }
-        pf.emplace_back();
-        pslot.push_back(-1);
-        fop& F = pf.back();
-        F.t1 = local_bit(lo);
-        F.t2 = local_bit(hi);
-        F.mat = (uint32_t)mo;
-        const uint32_t kind = all_diag ? FK_DIAG : (R == 2 ? FK_Q1 : FK_Q2);
-        F.kind = kind | (any_grad ? FOP_GAMMA : 0u);
-        it.writes_f = true;
-        const int n = all_diag ? 4 : R * R;
-        for (int i = 0; i < n; ++i) {
-          const cd va = all_diag ? Aup.a[i * 4 + i] : Aup.a[i];
-          const cdd vb = all_diag ? B.a[i * 4 + i] : B.a[i];
-          mats[mo + i] = cx{(real)va.real(), (real)va.imag()};
-          mats[mo + n + i] = cx{(real)vb.real(), (real)vb.imag()};
-        }
-        mo += 2 * n;
-        // complex MACs per amplitude: 1 (diagonal), 2 (one qubit), 4 (two qubits) per matrix
-        // applied (A; B too when two-state) and per Gamma accumulated; 8 real FLOPs each
-        const double cmac = all_diag ? 1.0 : (R == 2 ? 2.0 : 4.0);
-        it.flops_per_amp += 8.0 * cmac * ((two ? 2.0 : 1.0) + (any_grad ? 1.0 : 0.0));
-        if (any_grad) {
-          post.slot = next_slot++;
-          it.grad_slots.push_back(post.slot);
-          pslot.back() = (int)post.slot;
-          it.has_red = true;
-          stage_post.push_back(std::move(post));
-        }
-      }
-      // register-resident pass: f32, gate stages only (no densities / injections)
-      bool rq = use_rq && (sizeof(real) == 4 || rq64) && it.writes_f;
-      for (const fop& F : pf) rq = rq && (F.kind & 7u) <= FK_DIAG;
-      it.rq = rq;
-      if (!it.swaps.empty() && !rq)
-        return fail("internal: a permuting fused pass is not register-resident");
-      it.tbits = (uint32_t)LV + it.lc + it.h;
-      // the kernels index their per-wave accumulators by reduction op: a pass with more
-      // reduction ops than accumulators is a planner bug, never folded into another slot
-      {
-        const size_t nred = it.grad_slots.size();
-        const size_t cap = rq ? (size_t)FMAX_GRAD_RQ : (size_t)FMAX_GRAD;
-        if (nred > cap)
-          return fail("internal: a fused pass has %zu reduction ops, the kernel holds %zu", nred,
-                      cap);
-      }
-      if (!rq) {
-        for (const fop& F : pf) fops[fo++] = F;
-        it.nstage = (uint32_t)pf.size();
-        bool d1 = dens1_kernel && !two && !it.writes_f && !pf.empty() && pf.size() <= (size_t)DENS1_MAX;
-        for (const fop& F : pf) d1 = d1 && (F.kind & 7u) == FK_DENS1;
-        it.dens1 = d1;
-        continue;
-      }
-      auto put_layout = [&](const RqLayout& L) {
-        const rq_layout d = rq_descriptor(L, it.tbits);
-        const uint32_t off = (uint32_t)mo;
-        std::memcpy(&mats[mo], &d, sizeof d);
-        mo += sizeof(rq_layout) / sizeof(cx);
-        return off;
-      };
-      std::vector<RqStage> rs;
-      for (size_t k = 0; k < pf.size(); ++k) {
-        RqStage r{pf[k].kind & 7u, pf[k].t1, pf[k].t2, 0};
-        for (size_t i = 0; i < k; ++i)
-          if ((pq[i] & pq[k]) || (FusionPlanner::conflicts_of(pc[i]) & pc[k]) ||
-              (FusionPlanner::conflicts_of(pc[k]) & pc[i]))
-            r.deps |= 1ull << i;
-        rs.push_back(r);
-      }
-      // a permuting pass: tile bit t's value is stored where tile bit dest[t] sits
-      uint32_t dest[32], src[4] = {0, 1, 2, 3};
-      const bool perm = !it.swaps.empty();
-      if (perm) {
-        for (uint32_t t = 0; t < it.tbits; ++t) {
-          uint32_t p = t < (uint32_t)LV + it.lc ? t : (uint32_t)LV + it.hb[t - LV - it.lc];
-          for (const auto& sw : it.swaps) {
-            if (p == sw.first) p = sw.second;
-            else if (p == sw.second) p = sw.first;
-          }
-          dest[t] = local_bit(p);
-          if (dest[t] < 4) src[dest[t]] = t;
-        }
-      }
-      // the kernel variant that will run the pass: the plan's register slots come from it
-      QDC_TRY(rq_variant(two, it.tbits, it.var));
-      const RqVariant& V = *it.var;
-      const RqPlan& P = rq_plan_cached(rs, it.tbits, perm ? src : nullptr, rq_maxcl != 0, V.ns,
-                                       rq_keep(V));
-      it.l0 = put_layout(P.load);
-      {  // rqio after the load descriptor
-        rqio io{};
-        rq_hbm(P.load, it.tbits, it.lc, it.hb, io.gv_ld, io.offi_ld);
-        rq_hbm(P.store, it.tbits, it.lc, it.hb, io.gv_st, io.offi_st, perm ? dest : nullptr);
-        // gapped offsets (interleaved pair): the kernel gaps only the tile base, and the gap
-        // is linear over the disjoint bit sets of base, thread and register offsets
-        for (uint64_t* a : {io.gv_ld, io.gv_st})
-          for (int k = 0; k < 8; ++k) a[k] += a[k] & gm;
-        for (uint64_t* a : {io.offi_ld, io.offi_st})
-          for (int k = 0; k < RQ_R; ++k) a[k] += a[k] & gm;
-        std::memcpy(&mats[mo], &io, sizeof io);
-        mo += sizeof(rqio) / sizeof(cx);
-      }
-      uint32_t n = 0;
-      it.grad_slots.clear();  // the kernel reduces Gamma stages in execution order
-      // the variant's specialized pass (one-state passes: QDC_SPEC_FWD)
-      const bool spec = V.prefix && spec_on() && (two || spec_fwd);
-      std::vector<SpecStep> sst;
-      RqLayout lcur = P.load;
-      it.spec = nullptr;
-      for (const RqStep& step : P.steps) {
-        if (!step.relayout && pslot[step.stage] >= 0)
-          it.grad_slots.push_back((uint32_t)pslot[step.stage]);
-        fop F{};
-        if (step.relayout) {
-          F.kind = FK_RELAYOUT;
-          F.mat = put_layout(step.L);
-          if (spec) sst.push_back(SpecStep{true, lcur, step.L, F});
-          lcur = step.L;
-        } else {
-          F = pf[step.stage];
-          F.t1 = step.cs;
-          F.t2 = 0;
-          // two-qubit / diagonal stages run with the lower slot first (half the kernel's
-          // cases): exchange t1 and t2 by permuting the matrices' index bits, and the
-          // stage's Gamma back on the host
-          const uint32_t kd = F.kind & 7u;
-          if ((kd == FK_Q2 || kd == FK_DIAG) && (step.cs >> 3) > (step.cs & 7u)) {
-            F.t1 = (step.cs & 7u) * 8u + (step.cs >> 3);
-            const int nm = kd == FK_DIAG ? 4 : 16;
-            for (int h = 0; h < 2; ++h) {  // A, then B
-              cx* m = &mats[F.mat + (size_t)h * nm];
-              cx t[16];
-              for (int i = 0; i < nm; ++i) t[i] = m[i];
-              for (int i = 0; i < nm; ++i)
-                m[i] = kd == FK_DIAG ? t[swap_bits4(i)]
-                                     : t[swap_bits4(i >> 2) * 4 + swap_bits4(i & 3)];
-            }
-            if (pslot[step.stage] >= 0)
-              for (StagePost& sp : stage_post)
-                if (sp.slot == (uint32_t)pslot[step.stage]) sp.swapped = true;
-          }
-        }
-        if (spec && !step.relayout) sst.push_back(SpecStep{false, lcur, lcur, F});
-        fops[fo++] = F;
-        ++n;
-      }
-      it.nstage = n;
-      if (spec) {
-        // the source is generated once per distinct program (per process): the key is
-        // everything it depends on, the layouts, stage kinds, slot cases and Γ flags
-        const bool half = V.pass_half && spec_half && !spec_imm() && spec_half_ok(sst);
-        std::vector<uint32_t> key = {(uint32_t)(&V - rq_variants()), it.tbits, spec_imm() ? 1u : 0u,
-                                     half ? 1u : 0u};
-        auto put_layout_key = [&](const RqLayout& L) {
-          key.push_back(L.ns | (L.tfix ? 0x100u : 0u));
-          for (uint32_t q = 0; q < RQ_SLOTS_MAX; ++q) key.push_back(L.slot[q]);
-          for (int q = 0; q < 3; ++q) key.push_back(L.tfirst[q]);
-        };
-        put_layout_key(P.load);
-        for (const SpecStep& ss : sst) {
-          if (ss.relayout) {
-            key.push_back(0xffffffffu);
-            put_layout_key(ss.Ln);
-          } else {
-            key.push_back(ss.F.kind);
-            key.push_back(ss.F.t1);
-          }
-        }
-        auto hit = spec_cache.find(key);
-        if (hit == spec_cache.end()) {
-          const SpecKind K = spec_kind(V, half);
-          const std::string body = spec_program_source(sst, it.tbits, K);
-          SpecEntry e;
-          e.name = spec_kernel_name(body, K);
-          e.src = spec_kernel_source(e.name, body, K);
-          hit = spec_cache.emplace(std::move(key), std::move(e)).first;
-        }
-        it.spec = &hit->second;
-      }
-      if (rq_stats) fprintf(stderr, "rq pass: %zu stages, %u ops (T=%u lc=%u)\n", pf.size(), n, it.tbits, it.lc);
-      if (rq_stats >= 2) {  // the pass's stages for offline planner studies (tools/)
-        fprintf(stderr, "rq stages %s T=%u perm=%d:", two ? "two" : "one", it.tbits, perm ? 1 : 0);
-        for (const RqStage& r : rs)
-          fprintf(stderr, " %u,%u,%u,%llx", r.kind, r.t1, r.t2, (unsigned long long)r.deps);
-        fprintf(stderr, "\n");
-      }
-    }
-    if (dry) {  // the kernels this call would compile / load
-      for (Item& it : items)
-        if (it.spec && std::find(dry_specs.begin(), dry_specs.end(), it.spec) == dry_specs.end())
-          dry_specs.push_back(it.spec);
-      return nullptr;
-    }
-    for (auto& d : devs) {  // prog_host is not rewritten before the call's final sync
-      QDC_TRY(d->ctx.use());
-      QDC_HIP(hipMemcpyAsync(d->prog_dev, prog_host, mats_off + mo * sizeof(cx),
-                             hipMemcpyHostToDevice, d->ctx.stream));
-    }
-    QDC_TRY(spec_load(items));
     return nullptr;
+  }
+  // the tile-local amplitude bit of physical position p in the pass's tile
+  static uint32_t local_bit(const Item& it, uint32_t p) {
+    if (p < (uint32_t)LV + it.lc) return p;
+    for (uint32_t r = 0; r < it.h; ++r)
+      if (it.hb[r] == p - LV) return LV + it.lc + r;
+    return 0xffffffffu;  // unreachable: tile_config covered every bit
+  }
+  // Step 2: the pass's stage ops into B.ops, their matrices into the matrix area
+  const char* build_stages(Build& B, Item& it, size_t ii, bool two) {
+    it.fop_off = B.fo * sizeof(fop);
+    it.grad_slots.clear();
+    it.flops_per_amp = 0;
+    it.has_red = false;
+    it.writes_f = false;
+    B.ops.clear();
+    if (rec_mats) (*rec_mats)[ii].clear();
+    const FusionPlanner PL = planner();
+    for (size_t sj = 0; sj < it.stages.size(); ++sj) {
+      const auto& st = it.stages[sj];
+      StageOp so{fop{}, 0, 0, -1};
+      for (uint32_t pi : st) {
+        so.q |= (1ull << B.plan[pi].pos2) | (1ull << B.plan[pi].pos1);
+        so.cls |= PL.op_class(B.plan[pi], B.backward);
+      }
+      B.ops.push_back(so);
+      if (PL.is_meas(B.plan[st[0]]))
+        measure_stage(B, it, ii, B.plan[st[0]]);
+      else
+        QDC_TRY(gate_stage(B, it, ii, sj, two));
+    }
+    return nullptr;
+  }
+  // a density (forward) or a cotangent injection (backward)
+  void measure_stage(Build& B, Item& it, size_t ii, const qdc_plan_op& op) {
+    if (rec_mats) (*rec_mats)[ii].push_back(smat_identity(2));
+    const bool q1 = is_q1_density(ins[op.instr].kind);
+    const int R = q1 ? 2 : 4;
+    fop& F = B.ops.back().F;
+    F.t1 = local_bit(it, q1 ? op.pos2 : op.pos1);
+    F.t2 = local_bit(it, op.pos2);
+    F.mat = (uint32_t)B.mo;
+    cx* m = B.mats + B.mo;
+    for (int i = 0; i < 2 * R * R; ++i) m[i] = cx{0, 0};
+    if (B.backward) {  // b += (G^T on pos) (2 conj f), G = conj of the JAX cotangent
+      F.kind = q1 ? FK_INJ1 : FK_INJ2;
+      const qdc_complex* gd = B.dg->at(B.gidx[op.instr]);
+      if (q1) {
+        const mat<2> t = transpose<2>(to_mat<2>(gd));
+        for (int i = 0; i < 4; ++i) m[i] = t.a[i];
+      } else {
+        const mat<4> t = transpose<4>(to_mat<4>(gd));
+        for (int i = 0; i < 16; ++i) m[i] = t.a[i];
+      }
+    } else {
+      F.kind = q1 ? FK_DENS1 : FK_DENS2;
+      it.grad_slots.push_back(B.out_idx[op.instr]);
+      it.has_red = true;
+    }
+    it.flops_per_amp += 8.0 * (q1 ? 2.0 : 4.0);
+    B.mo += 2 * R * R;
+  }
+  // a stage of gates: compose it (qdc_stage.hpp), take the forward's adjoint where the pass
+  // mirrors one, record it for the trace, write its matrices A and B
+  const char* gate_stage(Build& B, Item& it, size_t ii, size_t sj, bool two) {
+    const auto& st = it.stages[sj];
+    // stage qubits (physical positions), lo < hi
+    const uint64_t qm = B.ops.back().q;
+    const uint32_t lo = (uint32_t)__builtin_ctzll(qm);
+    const uint32_t hi = 63u - (uint32_t)__builtin_clzll(qm);
+    const int R = lo == hi ? 2 : 4;
+    bool any_grad = false;
+    B.gates.clear();
+    for (uint32_t pi : st) {
+      const qdc_plan_op& op = B.plan[pi];
+      const Instr& in = ins[op.instr];
+      GateMats M;
+      QDC_TRY(gate_mats(in.kind, is_const(in.kind) ? B.cg.at(B.gidx[op.instr]) : B.vg.at(B.gidx[op.instr]),
+                        B.backward, M));
+      B.gates.emplace_back();
+      StageGateIn& g = B.gates.back();
+      for (int i = 0; i < M.count(); ++i) {
+        g.a[i] = cd(M.a[i].x, M.a[i].y);
+        g.b[i] = cdd(M.b[i].x, M.b[i].y);
+      }
+      g.diag = M.diag;
+      g.role = stage_role(R, is_q1_gate(in.kind), op.pos2, lo, hi);
+      const bool grad = two && is_var(in.kind);
+      g.var = grad ? (int)B.var_idx[op.instr] : -1;
+      any_grad = any_grad || grad;
+    }
+    SMat A;
+    SMatD Bp;
+    StagePost post;
+    stage_compose(B.gates.data(), B.gates.size(), R, A, Bp, post);
+    const bool all_diag = post.diag_only;
+    if (rec_mats) (*rec_mats)[ii].push_back(A);  // the forward's matrix, its own frame
+    SMat Aup = A;
+    const bool from_fwd = B.backward && mirror_adjoint(B.plan, it, sj, R, Aup);
+    if (tracing) {  // (physical positions; trace_logical maps them to logical qubits)
+      TraceOp t{B.backward ? 1u : 0u, (uint32_t)ii, hi, lo, (uint32_t)R, all_diag ? 1u : 0u,
+                from_fwd ? 1u : 0u, 0u, {}};
+      for (int i = 0; i < R * R; ++i) {
+        const bool keep = !all_diag || i % (R + 1) == 0;
+        t.m[i].re = keep ? (qdc_real)(real)Aup.a[i].real() : 0;
+        t.m[i].im = keep ? (qdc_real)(real)Aup.a[i].imag() : 0;
+      }
+      trace.push_back(t);
+    }
+    fop& F = B.ops.back().F;
+    F.t1 = local_bit(it, lo);
+    F.t2 = local_bit(it, hi);
+    F.mat = (uint32_t)B.mo;
+    F.kind = (all_diag ? FK_DIAG : (R == 2 ? FK_Q1 : FK_Q2)) | (any_grad ? FOP_GAMMA : 0u);
+    it.writes_f = true;
+    const int nm = all_diag ? 4 : R * R;
+    cx* m = B.mats + B.mo;
+    for (int i = 0; i < nm; ++i) {
+      const cd va = all_diag ? Aup.a[i * 4 + i] : Aup.a[i];
+      const cdd vb = all_diag ? Bp.a[i * 4 + i] : Bp.a[i];
+      m[i] = cx{(real)va.real(), (real)va.imag()};
+      m[nm + i] = cx{(real)vb.real(), (real)vb.imag()};
+    }
+    B.mo += 2 * nm;
+    // complex MACs per amplitude: 1 (diagonal), 2 (one qubit), 4 (two qubits) per matrix
+    // applied (A; B too when two-state) and per Gamma accumulated; 8 real FLOPs each
+    const double cmac = all_diag ? 1.0 : (R == 2 ? 2.0 : 4.0);
+    it.flops_per_amp += 8.0 * cmac * ((two ? 2.0 : 1.0) + (any_grad ? 1.0 : 0.0));
+    if (any_grad) {
+      post.slot = B.next_slot++;
+      it.grad_slots.push_back(post.slot);
+      B.ops.back().slot = (int)post.slot;
+      it.has_red = true;
+      stage_post.push_back(std::move(post));
+    }
+    return nullptr;
+  }
+  // A mirrored backward stage of unitary gates uncomputes with exactly the adjoint of the matrix
+  // its forward stage applied (same rounding: Aup, true), where the forward recorded one of this
+  // basis.  The forward frame's two qubits may have swapped order under the forward pass's
+  // permutation: swapped when the forward's lower qubit now sits above the other.
+  bool mirror_adjoint(const std::vector<qdc_plan_op>& plan, const Item& it, size_t sj, int R,
+                      SMat& Aup) const {
+    if (it.mirror_of.empty()) return false;
+    for (uint32_t pi : it.stages[sj])
+      if (is_nonu(ins[plan[pi].instr].kind)) return false;
+    const auto& of = it.mirror_of[sj];
+    if (of.first >= mrec.stage_mats.size() || of.second >= mrec.stage_mats[of.first].size())
+      return false;
+    const SMat& Pf = mrec.stage_mats[of.first][of.second];
+    if (Pf.R != R) return false;
+    const Item& f = mrec.items[of.first];
+    uint32_t flo = 64, fhi = 0;
+    for (uint32_t fi : f.stages[of.second]) {
+      const qdc_plan_op& fo = mrec.plan[fi];
+      flo = std::min({flo, fo.pos2, fo.pos1});
+      fhi = std::max({fhi, fo.pos2, fo.pos1});
+    }
+    Aup = stage_mirror_adjoint(Pf, R == 4 && apply_swaps(f.swaps, flo) > apply_swaps(f.swaps, fhi));
+    return true;
+  }
+  // Step 3: which kernel runs the pass.  Register-resident: gate stages only (no densities /
+  // injections), f32 or rq64; else the LDS kernel, or k_dens1 for a read-only pass of one-qubit
+  // densities.
+  const char* classify_pass(const Build& B, Item& it, bool two) const {
+    bool rq = use_rq && (sizeof(real) == 4 || rq64) && it.writes_f;
+    for (const StageOp& o : B.ops) rq = rq && (o.F.kind & 7u) <= FK_DIAG;
+    it.rq = rq;
+    if (!it.swaps.empty() && !rq)
+      return fail("internal: a permuting fused pass is not register-resident");
+    it.tbits = (uint32_t)LV + it.lc + it.h;
+    // the kernels index their per-wave accumulators by reduction op: a pass with more
+    // reduction ops than accumulators is a planner bug, never folded into another slot
+    const size_t nred = it.grad_slots.size();
+    const size_t cap = rq ? (size_t)FMAX_GRAD_RQ : (size_t)FMAX_GRAD;
+    if (nred > cap)
+      return fail("internal: a fused pass has %zu reduction ops, the kernel holds %zu", nred, cap);
+    if (rq) return nullptr;
+    bool d1 = dens1_kernel && !two && !it.writes_f && !B.ops.empty() && B.ops.size() <= (size_t)DENS1_MAX;
+    for (const StageOp& o : B.ops) d1 = d1 && (o.F.kind & 7u) == FK_DENS1;
+    it.dens1 = d1;
+    return nullptr;
+  }
+  // Step 4, LDS kernel: the stage ops as they are
+  static void emit_lds_pass(Build& B, Item& it) {
+    for (const StageOp& o : B.ops) B.fops[B.fo++] = o.F;
+    it.nstage = (uint32_t)B.ops.size();
+  }
+  uint32_t put_layout(Build& B, const RqLayout& L, uint32_t tbits) const {
+    const rq_layout d = rq_descriptor(L, tbits);
+    const uint32_t off = (uint32_t)B.mo;
+    std::memcpy(&B.mats[B.mo], &d, sizeof d);
+    B.mo += sizeof(rq_layout) / sizeof(cx);
+    return off;
+  }
+  // Step 4, register-resident kernel: the stages' dependencies, the kernel variant, the
+  // register-layout plan (rq_plan), the load descriptor and the HBM address tables (rqio), then
+  // the plan's steps — relayouts with their descriptors, stages with their slot case
+  const char* emit_rq_pass(Build& B, Item& it, bool two) {
+    B.rs.clear();
+    for (size_t k = 0; k < B.ops.size(); ++k) {
+      const StageOp& ok = B.ops[k];
+      RqStage r{ok.F.kind & 7u, ok.F.t1, ok.F.t2, 0};
+      for (size_t i = 0; i < k; ++i)
+        if ((B.ops[i].q & ok.q) || (FusionPlanner::conflicts_of(B.ops[i].cls) & ok.cls) ||
+            (FusionPlanner::conflicts_of(ok.cls) & B.ops[i].cls))
+          r.deps |= 1ull << i;
+      B.rs.push_back(r);
+    }
+    // a permuting pass: tile bit t's value is stored where tile bit dest[t] sits
+    uint32_t dest[32], src[4] = {0, 1, 2, 3};
+    const bool perm = !it.swaps.empty();
+    if (perm) {
+      for (uint32_t t = 0; t < it.tbits; ++t) {
+        const uint32_t p = t < (uint32_t)LV + it.lc ? t : (uint32_t)LV + it.hb[t - LV - it.lc];
+        dest[t] = local_bit(it, apply_swaps(it.swaps, p));
+        if (dest[t] < 4) src[dest[t]] = t;
+      }
+    }
+    // the kernel variant that will run the pass: the plan's register slots come from it
+    QDC_TRY(rq_variant(two, it.tbits, it.var));
+    const RqVariant& V = *it.var;
+    const RqPlan& P = rq_plan_cached(B.rs, it.tbits, perm ? src : nullptr, rq_maxcl != 0, V.ns,
+                                     rq_keep(V));
+    it.l0 = put_layout(B, P.load, it.tbits);
+    {  // rqio after the load descriptor
+      rqio io{};
+      rq_hbm(P.load, it.tbits, it.lc, it.hb, io.gv_ld, io.offi_ld);
+      rq_hbm(P.store, it.tbits, it.lc, it.hb, io.gv_st, io.offi_st, perm ? dest : nullptr);
+      // gapped offsets (interleaved pair): the kernel gaps only the tile base, and the gap
+      // is linear over the disjoint bit sets of base, thread and register offsets
+      for (uint64_t* a : {io.gv_ld, io.gv_st})
+        for (int k = 0; k < 8; ++k) a[k] += a[k] & gm;
+      for (uint64_t* a : {io.offi_ld, io.offi_st})
+        for (int k = 0; k < RQ_R; ++k) a[k] += a[k] & gm;
+      std::memcpy(&B.mats[B.mo], &io, sizeof io);
+      B.mo += sizeof(rqio) / sizeof(cx);
+    }
+    uint32_t nfop = 0;
+    it.grad_slots.clear();  // the kernel reduces Gamma stages in execution order
+    // the variant's specialized pass (one-state passes: QDC_SPEC_FWD)
+    const bool spec = V.prefix && spec_on() && (two || spec_fwd);
+    B.sst.clear();
+    RqLayout lcur = P.load;
+    for (const RqStep& step : P.steps) {
+      fop F{};
+      if (step.relayout) {
+        F.kind = FK_RELAYOUT;
+        F.mat = put_layout(B, step.L, it.tbits);
+        if (spec) B.sst.push_back(SpecStep{true, lcur, step.L, F});
+        lcur = step.L;
+      } else {
+        const int slot = B.ops[step.stage].slot;
+        if (slot >= 0) it.grad_slots.push_back((uint32_t)slot);
+        F = B.ops[step.stage].F;
+        F.t1 = step.cs;
+        F.t2 = 0;
+        // two-qubit / diagonal stages run with the lower slot first (half the kernel's
+        // cases): exchange t1 and t2 by permuting the matrices' index bits, and the
+        // stage's Gamma back on the host
+        const uint32_t kd = F.kind & 7u;
+        if ((kd == FK_Q2 || kd == FK_DIAG) && (step.cs >> 3) > (step.cs & 7u)) {
+          F.t1 = (step.cs & 7u) * 8u + (step.cs >> 3);
+          stage_swap_slots(&B.mats[F.mat], kd == FK_DIAG);
+          if (slot >= 0)
+            for (StagePost& sp : stage_post)
+              if (sp.slot == (uint32_t)slot) sp.swapped = true;
+        }
+        if (spec) B.sst.push_back(SpecStep{false, lcur, lcur, F});
+      }
+      B.fops[B.fo++] = F;
+      ++nfop;
+    }
+    it.nstage = nfop;
+    it.spec = spec ? spec_entry(B, V, it.tbits, P.load) : nullptr;
+    if (rq_stats)
+      fprintf(stderr, "rq pass: %zu stages, %u ops (T=%u lc=%u)\n", B.ops.size(), nfop, it.tbits, it.lc);
+    if (rq_stats >= 2) {  // the pass's stages for offline planner studies (tools/)
+      fprintf(stderr, "rq stages %s T=%u perm=%d:", two ? "two" : "one", it.tbits, perm ? 1 : 0);
+      for (const RqStage& r : B.rs)
+        fprintf(stderr, " %u,%u,%u,%llx", r.kind, r.t1, r.t2, (unsigned long long)r.deps);
+      fprintf(stderr, "\n");
+    }
+    return nullptr;
+  }
+  // Step 5: the specialized kernel of the pass whose steps are B.sst, from spec_cache.  The
+  // source is generated once per distinct program (per process): the key is everything it
+  // depends on, the layouts, stage kinds, slot cases and Gamma flags
+  SpecEntry* spec_entry(Build& B, const RqVariant& V, uint32_t tbits, const RqLayout& load) {
+    const bool half = V.pass_half && spec_half && !spec_imm() && spec_half_ok(B.sst);
+    std::vector<uint32_t>& key = B.key;
+    key.assign({(uint32_t)(&V - rq_variants()), tbits, spec_imm() ? 1u : 0u, half ? 1u : 0u});
+    auto put_layout_key = [&](const RqLayout& L) {
+      key.push_back(L.ns | (L.tfix ? 0x100u : 0u));
+      for (uint32_t q = 0; q < RQ_SLOTS_MAX; ++q) key.push_back(L.slot[q]);
+      for (int q = 0; q < 3; ++q) key.push_back(L.tfirst[q]);
+    };
+    put_layout_key(load);
+    for (const SpecStep& ss : B.sst) {
+      if (ss.relayout) {
+        key.push_back(0xffffffffu);
+        put_layout_key(ss.Ln);
+      } else {
+        key.push_back(ss.F.kind);
+        key.push_back(ss.F.t1);
+      }
+    }
+    auto hit = spec_cache.find(key);
+    if (hit == spec_cache.end()) {
+      const SpecKind K = spec_kind(V, half);
+      const std::string body = spec_program_source(B.sst, tbits, K);
+      SpecEntry e;
+      e.name = spec_kernel_name(body, K);
+      e.src = spec_kernel_source(e.name, body, K);
+      hit = spec_cache.emplace(key, std::move(e)).first;
+    }
+    return &hit->second;
   }
   // specialized passes: circuits of >= spec_min_qubits local qubits (every shard runs the same
   // program; the kernels are loaded on each shard's device)
@@ -1524,11 +1536,6 @@ struct Circuit {
   }
   // Run one fused group on every shard.  grads != nullptr: two-state reverse program whose
   // gradient gates write partials for gradient buffer rows var_idx[...].
-  template <bool TWO, bool HASRED, bool WF, int NT>
-  static auto fused_kernel() {
-    constexpr int TB = TWO ? (int)TILE_CHUNKS_2 : (int)TILE_CHUNKS_1;
-    return k_fused<TWO, TB, HASRED, WF, NT>;
-  }
   template <bool TWO, bool HASRED, bool WF>
   const char* launch_fused(Ctx& ctx, const char* name, double bytes, const fgeo& fg, chunk* f,
                            chunk* b, const fop* fops, const cx* mats, cx* partials,
@@ -1585,7 +1592,7 @@ struct Circuit {
     return ctx.launch_block(name, bytes, kern, grid, (uint32_t)NT, (const chunk*)f, fops, g,
                             partials, stride);
   }
-  // register-resident pass (qdc_rq.hpp) on its kernel variant V (build_program's choice,
+  // register-resident pass (qdc_rq.hpp) on its kernel variant V (emit_rq_pass's choice,
   // qdc_variant.hpp), or on the pass's own specialized kernel where one is loaded: the same
   // block size, tile shares and arguments either way
   const char* launch_rq(Ctx& ctx, const char* name, double bytes, const fgeo& fg, bool two,
@@ -1594,7 +1601,7 @@ struct Circuit {
                         hipFunction_t spec = nullptr) {
     if (!V || V->two != two || V->tbits != tbits || (spec && !V->prefix))
       return fail("internal: a register-resident pass without its kernel variant");
-    // a register-resident pass holds gate stages only (build_program), and only two-state
+    // a register-resident pass holds gate stages only (classify_pass), and only two-state
     // stages accumulate Gamma: a one-state pass never reduces.  Its dynamic tail (no granule
     // partials) and the one-state kernels (no reduction code) rest on that.
     if (!two && fg.ngrad > 0)
@@ -1716,36 +1723,22 @@ struct Circuit {
   }
 
   // --- forward (Circuit::run / Circuit::forward) --------------------------------------------
+  // one gate on one state: forward, or (uncompute) the reverse sweep before its first cotangent
   const char* apply_gate(Ctx& ctx, const Instr& in, const qdc_complex* g4, cx* s, uint32_t p2,
                          uint32_t p1, bool uncompute) {
-    if (is_diag(in.kind)) {
-      const diag4 d = to_diag(g4);
-      return apply_diag(ctx, s, uncompute ? conj_diag(d) : d, p2, p1, nl,
+    GateMats M;
+    QDC_TRY(gate_mats(in.kind, g4, uncompute, M));
+    if (M.diag)
+      return apply_diag(ctx, s, GateMats::diagonal(M.a), p2, p1, nl,
                         uncompute ? "uncompute_q2_diag" : "apply_q2_diag");
-    }
-    if (is_q1_gate(in.kind)) {
-      const mat<2> u = to_mat<2>(g4);
-      mat<2> a = u;
-      if (uncompute) {
-        if (is_nonu(in.kind))
-          QDC_TRY(inverse<2>(u, a));
-        else
-          a = conj_transpose<2>(u);
-      }
-      return apply_dense<2>(ctx, s, a, p2, p2, nl, uncompute ? "uncompute_q1" : "apply_q1");
-    }
-    const mat<4> u = to_mat<4>(g4);
-    mat<4> a = u;
-    if (uncompute) {
-      if (is_nonu(in.kind))
-        QDC_TRY(inverse<4>(u, a));
-      else
-        a = conj_transpose<4>(u);
-    }
-    return apply_dense<4>(ctx, s, a, p2, p1, nl, uncompute ? "uncompute_q2" : "apply_q2");
+    if (M.R == 2)
+      return apply_dense<2>(ctx, s, GateMats::dense<2>(M.a), p2, p2, nl,
+                            uncompute ? "uncompute_q1" : "apply_q1");
+    return apply_dense<4>(ctx, s, GateMats::dense<4>(M.a), p2, p1, nl,
+                          uncompute ? "uncompute_q2" : "apply_q2");
   }
 
-  // The trace entries of this call's fused stages (build_program, physical positions) mapped to
+  // The trace entries of this call's fused stages (gate_stage, physical positions) mapped to
   // logical qubits by replaying the call's layout changes (remaps, undone remaps, permuting
   // passes' swaps) from `layout` (the call's start), with the single-gate items' matrices (as
   // apply_gate / reverse_dense apply them) inserted in item order.  Dry runs only.
@@ -1777,36 +1770,12 @@ struct Circuit {
           const qdc_complex* g4 = is_const(in.kind) ? cg.at(gidx[op.instr]) : vg.at(gidx[op.instr]);
           TraceOp s{backward ? 1u : 0u, (uint32_t)ii, m.logi[op.pos2], m.logi[op.pos1], 4u,
                     is_diag(in.kind) ? 1u : 0u, 0u, 1u, {}};
-          auto put = [&](const cx* a, int R) {
-            s.R = (uint32_t)R;
-            for (int i = 0; i < R * R; ++i) s.m[i] = qdc_complex{(qdc_real)a[i].x, (qdc_real)a[i].y};
-          };
-          if (is_diag(in.kind)) {
-            const diag4 d0 = to_diag(g4);
-            const diag4 d = backward ? conj_diag(d0) : d0;
-            for (int i = 0; i < 4; ++i) s.m[i * 5] = qdc_complex{(qdc_real)d.a[i].x, (qdc_real)d.a[i].y};
-          } else if (is_q1_gate(in.kind)) {
-            const mat<2> u = to_mat<2>(g4);
-            mat<2> a = u;
-            if (backward) {
-              if (is_nonu(in.kind))
-                QDC_TRY(inverse<2>(u, a));
-              else
-                a = conj_transpose<2>(u);
-            }
-            s.q1 = s.q2;
-            put(a.a, 2);
-          } else {
-            const mat<4> u = to_mat<4>(g4);
-            mat<4> a = u;
-            if (backward) {
-              if (is_nonu(in.kind))
-                QDC_TRY(inverse<4>(u, a));
-              else
-                a = conj_transpose<4>(u);
-            }
-            put(a.a, 4);
-          }
+          GateMats M;
+          QDC_TRY(gate_mats(in.kind, g4, backward, M));
+          s.R = (uint32_t)M.R;
+          if (M.R == 2) s.q1 = s.q2;
+          for (int i = 0; i < M.count(); ++i)  // (a diagonal expanded)
+            s.m[M.diag ? i * 5 : i] = qdc_complex{(qdc_real)M.a[i].x, (qdc_real)M.a[i].y};
           trace.push_back(s);
         }
       }
@@ -1828,7 +1797,10 @@ struct Circuit {
     ht[0] = hclock::now();
     std::vector<size_t> gidx;
     QDC_TRY(validate_forward(cg, vg, gidx));
-    const size_t nout = output_count(mode);
+    std::vector<uint32_t> out_idx;
+    std::vector<int> widths;
+    outputs(mode, out_idx, widths);
+    const size_t nout = widths.size();
     if (!dry) {
       QDC_TRY(dyn_reset_all());
       QDC_TRY(ensure_out(true, std::max<size_t>(nout, 1) * RED));
@@ -1838,13 +1810,6 @@ struct Circuit {
     for (auto& s : sh) {
       QDC_TRY(s.c().use());
       QDC_TRY(copy_initial(s));
-    }
-    std::vector<uint32_t> out_idx(ins.size(), 0);
-    {
-      uint32_t o = 0;
-      for (size_t k = 0; k < ins.size(); ++k)
-        if (is_diff_density(ins[k].kind) || (mode == QDC_MODE_RUN && is_density(ins[k].kind)))
-          out_idx[k] = o++;
     }
     mark_inexact(cg, vg, gidx);
     ht[1] = hclock::now();
@@ -1863,16 +1828,7 @@ struct Circuit {
     rec_mats = nullptr;
     QDC_TRY(berr);
     ht[3] = hclock::now();
-    if (record) {
-      mrec.plan = pl;
-      mrec.items = items;
-      mrec.stage_mats = std::move(mats_rec);
-      const size_t nc = cg.size() ? cg.off.back() + cg.len.back() : 0;
-      const size_t nv = vg.size() ? vg.off.back() + vg.len.back() : 0;
-      mrec.cgates.assign(cg.data, cg.data + nc);
-      mrec.vgates.assign(vg.data, vg.data + nv);
-      mrec.inexact = inexact;
-    }
+    if (record) mrec.capture(cg, vg, pl, items, std::move(mats_rec), inexact);
     if (rq_stats)
       fprintf(stderr, "forward plan+build %.3f ms\n",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count());
@@ -1921,10 +1877,6 @@ struct Circuit {
     std::vector<cx*> bufs;
     for (auto& s : sh) bufs.push_back(s.dens);
     QDC_TRY(ex.allreduce(sh, bufs, nout * RED));
-    std::vector<int> widths;
-    for (auto& in : ins)
-      if (is_diff_density(in.kind) || (mode == QDC_MODE_RUN && is_density(in.kind)))
-        widths.push_back(is_q1_density(in.kind) ? 4 : 16);
     QDC_TRY(collect(sh[0].dens, widths, out));
     ht[5] = hclock::now();
     host_record(0, ht);
@@ -2021,6 +1973,62 @@ struct Circuit {
   }
 
   // --- backward (Circuit::backward, circuit.rs:266-429) --------------------------------------
+  // apply_gate's counterpart on the state pair: uncompute f, pull b back and, for a variable
+  // gate, reduce its gradient into row dst of gbase
+  const char* reverse_gate(Ctx& ctx, const Instr& in, const qdc_complex* g4, cx* f, cx* b,
+                           uint32_t p2, uint32_t p1, cx* gbase, uint32_t dst) {
+    GateMats M;
+    QDC_TRY(gate_mats(in.kind, g4, true, M));
+    if (M.diag) return reverse_diag(ctx, f, b, GateMats::diagonal(M.b), p2, p1, nl, gbase, dst);
+    if (M.R == 2)
+      return reverse_dense<2>(ctx, f, b, GateMats::dense<2>(M.a), GateMats::dense<2>(M.b), p2, p2,
+                              nl, gbase, dst);
+    return reverse_dense<4>(ctx, f, b, GateMats::dense<4>(M.a), GateMats::dense<4>(M.b), p2, p1, nl,
+                            gbase, dst);
+  }
+  // one plan op of the reverse sweep outside the fused passes, on every shard: a gate (before the
+  // first cotangent it only uncomputes fwd), or a density's cotangent injection
+  const char* backward_op(const qdc_plan_op& op, const Flat& dg, const Flat& cg, const Flat& vg,
+                          const std::vector<size_t>& gidx, const std::vector<uint32_t>& var_idx,
+                          bool& have_bwd) {
+    const Instr& in = ins[op.instr];
+    const bool gate = is_const(in.kind) || is_var(in.kind), var = is_var(in.kind);
+    const qdc_complex* g4 = (!gate ? dg : var ? vg : cg).at(gidx[op.instr]);
+    for (auto& s : sh) {
+      Ctx& ctx = s.c();
+      QDC_TRY(ctx.use());
+      if (gate && !have_bwd)
+        QDC_TRY(apply_gate(ctx, in, g4, s.state, op.pos2, op.pos1, true));
+      else if (gate)
+        QDC_TRY(reverse_gate(ctx, in, g4, s.state, s.bwd, op.pos2, op.pos1, var ? s.grads : nullptr,
+                             var_idx[op.instr]));
+      else if (is_q1_density(in.kind))
+        QDC_TRY(inject<2>(ctx, s.state, s.bwd, transpose<2>(to_mat<2>(g4)), op.pos2, op.pos2, nl,
+                          !have_bwd));
+      else
+        QDC_TRY(inject<4>(ctx, s.state, s.bwd, transpose<4>(to_mat<4>(g4)), op.pos2, op.pos1, nl,
+                          !have_bwd));
+    }
+    if (!gate) have_bwd = true;
+    return nullptr;
+  }
+  // The backward's schedule: the forward's passes in reverse (mirror_schedule) when this backward
+  // follows that forward with the same gates, else its own plan, fused as usual
+  const char* schedule_backward(const Flat& cg, const Flat& vg, std::vector<qdc_plan_op>& pl,
+                                std::vector<Item>& items, size_t& first_inject) {
+    bool mirrored = false;
+    if (mirror_on() && mrec.valid && mrec.inexact == inexact && mrec.end_phys == layout.phys)
+      mirrored = mrec.same_gates(cg, vg) && mirror_schedule(pl, items, first_inject);
+    mrec.valid = false;  // (this backward changes the layout and the state)
+    if (mirrored) return nullptr;
+    pl = plan(QDC_PLAN_BACKWARD);
+    first_inject = first_injection(pl);
+    // QDC_MIRROR=2 (tests): a backward that cannot mirror its forward is an error
+    if (mirror_on() && mirror == 2)
+      return fail("mirror: the backward does not follow a forward call with the same gates");
+    items = schedule(pl, true, first_inject);
+    return nullptr;
+  }
   const char* backward(const Flat& dg, const Flat& cg, const Flat& vg, qdc_complex* out) {
     hclock::time_point ht[6];
     ht[0] = hclock::now();
@@ -2056,31 +2064,7 @@ struct Circuit {
     std::vector<qdc_plan_op> pl;
     std::vector<Item> items;
     size_t first_inject = 0;
-    // mirrored: the forward's passes in reverse, when this backward follows that forward with
-    // the same gates (else the backward schedules itself)
-    bool mirrored = false;
-    if (mirror_on() && mrec.valid && mrec.inexact == inexact && mrec.end_phys == layout.phys) {
-      const size_t nc = cg.size() ? cg.off.back() + cg.len.back() : 0;
-      const size_t nv = vg.size() ? vg.off.back() + vg.len.back() : 0;
-      const bool same = nc == mrec.cgates.size() && nv == mrec.vgates.size() &&
-                        (nc == 0 || std::memcmp(cg.data, mrec.cgates.data(), nc * sizeof(qdc_complex)) == 0) &&
-                        (nv == 0 || std::memcmp(vg.data, mrec.vgates.data(), nv * sizeof(qdc_complex)) == 0);
-      mirrored = same && mirror_schedule(pl, items, first_inject);
-    }
-    mrec.valid = false;  // (this backward changes the layout and the state)
-    if (!mirrored) {
-      pl = plan(QDC_PLAN_BACKWARD);
-      first_inject = pl.size();
-      for (size_t i = 0; i < pl.size(); ++i)
-        if (pl[i].type == QDC_PLAN_OP && is_diff_density(ins[pl[i].instr].kind)) {
-          first_inject = i;
-          break;
-        }
-      // QDC_MIRROR=2 (tests): a backward that cannot mirror its forward is an error
-      if (mirror_on() && mirror == 2)
-        return fail("mirror: the backward does not follow a forward call with the same gates");
-      items = schedule(pl, true, first_inject);
-    }
+    QDC_TRY(schedule_backward(cg, vg, pl, items, first_inject));
     if (diag_inject) merge_diag_injections(items, pl, dg, gidx);
     ht[2] = hclock::now();
     // a run of diagonal cotangent injections: one elementwise pass (no pass program)
@@ -2132,55 +2116,7 @@ struct Circuit {
         QDC_TRY(item.inv ? unremap(op, have_bwd) : remap(op, have_bwd));
         continue;
       }
-      const Instr& in = ins[op.instr];
-      if (is_const(in.kind) || is_var(in.kind)) {
-        const bool var = is_var(in.kind);
-        const qdc_complex* g4 = var ? vg.at(gidx[op.instr]) : cg.at(gidx[op.instr]);
-        for (auto& s : sh) {
-          Ctx& ctx = s.c();
-          QDC_TRY(ctx.use());
-          if (!have_bwd) {
-            QDC_TRY(apply_gate(ctx, in, g4, s.state, op.pos2, op.pos1, true));
-            continue;
-          }
-          cx* gbase = var ? s.grads : nullptr;
-          const uint32_t dst = var_idx[op.instr];
-          if (is_diag(in.kind)) {
-            QDC_TRY(reverse_diag(ctx, s.state, s.bwd, to_diag(g4), op.pos2, op.pos1, nl, gbase, dst));
-          } else if (is_q1_gate(in.kind)) {
-            const mat<2> u = to_mat<2>(g4);
-            mat<2> A;
-            if (is_nonu(in.kind))
-              QDC_TRY(inverse<2>(u, A));
-            else
-              A = conj_transpose<2>(u);
-            QDC_TRY(reverse_dense<2>(ctx, s.state, s.bwd, A, transpose<2>(u), op.pos2, op.pos2, nl,
-                                     gbase, dst));
-          } else {
-            const mat<4> u = to_mat<4>(g4);
-            mat<4> A;
-            if (is_nonu(in.kind))
-              QDC_TRY(inverse<4>(u, A));
-            else
-              A = conj_transpose<4>(u);
-            QDC_TRY(reverse_dense<4>(ctx, s.state, s.bwd, A, transpose<4>(u), op.pos2, op.pos1, nl,
-                                     gbase, dst));
-          }
-        }
-      } else {  // Diff density: inject its cotangent
-        const qdc_complex* gd = dg.at(gidx[op.instr]);
-        for (auto& s : sh) {
-          Ctx& ctx = s.c();
-          QDC_TRY(ctx.use());
-          if (is_q1_density(in.kind))
-            QDC_TRY(inject<2>(ctx, s.state, s.bwd, transpose<2>(to_mat<2>(gd)), op.pos2, op.pos2, nl,
-                              !have_bwd));
-          else
-            QDC_TRY(inject<4>(ctx, s.state, s.bwd, transpose<4>(to_mat<4>(gd)), op.pos2, op.pos1, nl,
-                              !have_bwd));
-        }
-        have_bwd = true;
-      }
+      QDC_TRY(backward_op(op, dg, cg, vg, gidx, var_idx, have_bwd));
     }
     ht[4] = hclock::now();
     QDC_TRY(flush_all());
@@ -2196,33 +2132,7 @@ struct Circuit {
     if (!stage_post.empty()) {
       std::vector<size_t> off(widths.size() + 1, 0);
       for (size_t j = 0; j < widths.size(); ++j) off[j + 1] = off[j] + widths[j];
-      for (const StagePost& st : stage_post) {
-        SMatD G = smat_identity<double>(st.R);
-        const cx* g = host_out + (size_t)st.slot * RED;
-        auto sw = [&](int p) { return st.swapped ? swap_bits4(p) : p; };
-        if (st.diag_only) {
-          for (int i = 0; i < 16; ++i) G.a[i] = 0;
-          for (int r = 0; r < 4; ++r) G.a[r * 4 + r] = cdd(g[sw(r)].x, g[sw(r)].y);
-        } else if (st.R == 4) {
-          for (int p = 0; p < 4; ++p)
-            for (int q = 0; q < 4; ++q) {
-              const cx v = g[sw(p) * 4 + sw(q)];
-              G.a[p * 4 + q] = cdd(v.x, v.y);
-            }
-        } else {
-          for (int i = 0; i < st.R * st.R; ++i) G.a[i] = cdd(g[i].x, g[i].y);
-        }
-        for (const StageGate& sg : st.gates) {
-          const SMatD M = smat_mul(smat_mul(sg.L, G), sg.Rt);
-          cdd v[16];
-          stage_extract(M, sg.diag, sg.role, v);
-          qdc_complex* o = out + off[sg.var];
-          for (int k = 0; k < widths[sg.var]; ++k) {
-            o[k].re = (qdc_real)v[k].real();
-            o[k].im = (qdc_real)v[k].imag();
-          }
-        }
-      }
+      stage_gradients(stage_post, host_out, (size_t)RED, off, widths, out);
     }
     ht[5] = hclock::now();
     host_record(1, ht);

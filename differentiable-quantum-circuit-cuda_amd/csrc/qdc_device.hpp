@@ -735,6 +735,55 @@ inline const char* inverse(const mat<R>& a, mat<R>& out) {
   return nullptr;
 }
 
+// The matrix a gate applies and its pull-back: the one statement of the uncompute rule, shared
+// by the fused stages, the single-gate kernels and the dry-run trace.  Forward: a = U.
+// Uncompute: a = U^-1 for a non-unitary kind (inverse<> and its error), U^dagger otherwise, the
+// conjugate diagonal for a diagonal gate.  Pull-back: b = U^T (diagonal: d).  Both row-major in
+// the gate's own basis, count() entries.
+struct GateMats {
+  int R = 4;  // 2 or 4 (a diagonal: 4)
+  bool diag = false;
+  cx a[16], b[16];
+  int count() const { return diag ? 4 : R * R; }
+  template <int N>
+  static mat<N> dense(const cx* v) {
+    mat<N> m;
+    for (int i = 0; i < N * N; ++i) m.a[i] = v[i];
+    return m;
+  }
+  static diag4 diagonal(const cx* v) { return diag4{{v[0], v[1], v[2], v[3]}}; }
+};
+template <int R>
+inline const char* gate_mats_dense(const qdc_complex* g, bool nonu, bool uncompute, GateMats& m) {
+  const mat<R> u = to_mat<R>(g);
+  mat<R> a = u;
+  if (uncompute) {
+    if (nonu)
+      QDC_TRY(inverse<R>(u, a));
+    else
+      a = conj_transpose<R>(u);
+  }
+  const mat<R> bt = transpose<R>(u);
+  for (int i = 0; i < R * R; ++i) {
+    m.a[i] = a.a[i];
+    m.b[i] = bt.a[i];
+  }
+  return nullptr;
+}
+inline const char* gate_mats(const qdc_complex* g, bool diag, bool q1, bool nonu, bool uncompute,
+                             GateMats& m) {
+  m.diag = diag;
+  m.R = q1 ? 2 : 4;
+  if (!diag) return q1 ? gate_mats_dense<2>(g, nonu, uncompute, m) : gate_mats_dense<4>(g, nonu, uncompute, m);
+  const diag4 d = to_diag(g);
+  const diag4 a = uncompute ? conj_diag(d) : d;
+  for (int i = 0; i < 4; ++i) {
+    m.a[i] = a.a[i];
+    m.b[i] = d.a[i];
+  }
+  return nullptr;
+}
+
 // ---------------------------------------------------------------------------------------
 // Op launchers (all asynchronous on ctx.stream)
 // ---------------------------------------------------------------------------------------

@@ -270,7 +270,7 @@ __device__ __forceinline__ void rq_q1(cx (&f)[R], cx (&b)[R], const cx* __restri
 }
 
 // one register stage: slot case (host: rq_plan) two-qubit / diagonal S1 * 8 + S2 (t1 in slot
-// S1, t2 in slot S2, always S1 < S2: build_program exchanges t1 and t2 otherwise); one-qubit:
+// S1, t2 in slot S2, always S1 < S2: emit_rq_pass exchanges t1 and t2 otherwise); one-qubit:
 // the slot of t1
 template <bool TWO, int R>
 __device__ __forceinline__ void rq_stage(uint32_t sel, cx (&xf)[R], cx (&xb)[R],
@@ -584,7 +584,7 @@ __device__ __forceinline__ void rq_pass(chunk* __restrict__ f, chunk* __restrict
       const uint32_t kind = op.kind & 7u;
       const bool gamma = TWO && (op.kind & FOP_GAMMA) && !(QDC_RQ_ABL & 4);
       const cx* M = mats + op.mat;
-      // ri < FMAX_GRAD_RQ: build_program rejects a pass with more Gamma stages
+      // ri < FMAX_GRAD_RQ: classify_pass rejects a pass with more Gamma stages
       real* acc = TWO ? &accw[wave][ri][0] : nullptr;
       if ((QDC_RQ_ABL & 2) && kind == FK_RELAYOUT) {
         lcur = op.mat;

@@ -185,4 +185,102 @@ struct StagePost {
   std::vector<StageGate> gates;
 };
 
+// The role of a gate at pos2 (one-qubit: its position) in a stage on qubits lo <= hi of basis R.
+inline int stage_role(int R, bool q1, uint32_t pos2, uint32_t lo, uint32_t hi) {
+  if (R == 2) return ROLE_Q1_ONLY;
+  if (q1) return pos2 == lo ? ROLE_Q1_LO : ROLE_Q1_HI;
+  return pos2 == hi ? ROLE_Q2 : ROLE_Q2_SWAP;
+}
+
+// One gate of a stage as stage_compose takes it: the applied matrix a and the pull-back b, each
+// in the gate's own basis (4 entries for a 2x2 or a diagonal, else 16).
+struct StageGateIn {
+  cd a[16];
+  cdd b[16];
+  bool diag;
+  int role;
+  int var;  // gradient row of a variable gate of a two-state pass, else -1
+};
+
+// Compose a stage of basis R from its n gates in program order: A = a_n ... a_1, B = b_n ... b_1
+// and the gradient recipe of every gate that has one (post.gates, post.R, post.diag_only).
+inline void stage_compose(const StageGateIn* g, size_t n, int R, SMat& A, SMatD& B, StagePost& post) {
+  A = smat_identity(R);
+  B = smat_identity<double>(R);
+  post.R = R;
+  post.diag_only = true;
+  for (size_t k = 0; k < n; ++k) {
+    post.diag_only = post.diag_only && g[k].diag;
+    const SMat Ea = stage_embed(g[k].a, g[k].diag, g[k].role, R);
+    const SMatD Eb = stage_embed(g[k].b, g[k].diag, g[k].role, R);
+    const SMat Anew = smat_mul(Ea, A);
+    if (g[k].var >= 0)
+      post.gates.push_back(StageGate{(uint32_t)g[k].var, g[k].diag, g[k].role, B,
+                                     smat_double(smat_transpose(Anew))});
+    A = Anew;
+    B = smat_mul(Eb, B);
+  }
+}
+
+// The matrix a mirrored reverse stage applies: the adjoint of the matrix Pf its forward stage
+// applied (same rounding).  swapped: the forward frame's two qubits have exchanged order since.
+inline SMat stage_mirror_adjoint(const SMat& Pf, bool swapped) {
+  SMat At = Pf;
+  const int R = Pf.R;
+  for (int p = 0; p < R; ++p)
+    for (int q = 0; q < R; ++q) {
+      const int sp = swapped ? swap_bits4(p) : p, sq = swapped ? swap_bits4(q) : q;
+      At.a[p * R + q] = std::conj(Pf.a[sq * R + sp]);
+    }
+  return At;
+}
+
+// Exchange the two index bits of a stage's uploaded matrices, A then B behind it (each 16
+// entries, or the 4 of a diagonal): the stage then runs with the lower register slot first.
+template <class C>
+inline void stage_swap_slots(C* m, bool diag) {
+  const int nm = diag ? 4 : 16;
+  for (int h = 0; h < 2; ++h, m += nm) {
+    C t[16];
+    for (int i = 0; i < nm; ++i) t[i] = m[i];
+    for (int i = 0; i < nm; ++i)
+      m[i] = diag ? t[swap_bits4(i)] : t[swap_bits4(i >> 2) * 4 + swap_bits4(i & 3)];
+  }
+}
+
+// Gradients of the fused stages' variable gates, G = ptrace(L Gamma Rt) per gate, from the
+// read-back reduction slots (Gamma of stage st at slots + st.slot * stride; C has x, y) into
+// `out` (O has re, im), gate `var` at off[var] with widths[var] values.
+template <class C, class O>
+inline void stage_gradients(const std::vector<StagePost>& posts, const C* slots, size_t stride,
+                            const std::vector<size_t>& off, const std::vector<int>& widths, O* out) {
+  for (const StagePost& st : posts) {
+    SMatD G = smat_identity<double>(st.R);
+    const C* g = slots + (size_t)st.slot * stride;
+    auto sw = [&](int p) { return st.swapped ? swap_bits4(p) : p; };
+    if (st.diag_only) {
+      for (int i = 0; i < 16; ++i) G.a[i] = 0;
+      for (int r = 0; r < 4; ++r) G.a[r * 4 + r] = cdd(g[sw(r)].x, g[sw(r)].y);
+    } else if (st.R == 4) {
+      for (int p = 0; p < 4; ++p)
+        for (int q = 0; q < 4; ++q) {
+          const C v = g[sw(p) * 4 + sw(q)];
+          G.a[p * 4 + q] = cdd(v.x, v.y);
+        }
+    } else {
+      for (int i = 0; i < st.R * st.R; ++i) G.a[i] = cdd(g[i].x, g[i].y);
+    }
+    for (const StageGate& sg : st.gates) {
+      const SMatD M = smat_mul(smat_mul(sg.L, G), sg.Rt);
+      cdd v[16];
+      stage_extract(M, sg.diag, sg.role, v);
+      O* o = out + off[sg.var];
+      for (int k = 0; k < widths[sg.var]; ++k) {
+        o[k].re = (decltype(o[k].re))v[k].real();
+        o[k].im = (decltype(o[k].im))v[k].imag();
+      }
+    }
+  }
+}
+
 }  // namespace qdc

@@ -4,7 +4,7 @@
 // A row says everything the host needs to know about a variant: the tile it runs, its block
 // size and register slots, whether its launch may take a dynamic tail (Ctx::plan_dyn), the
 // generic kernel, and — where the variant has one — the specialized pass that replaces the
-// generic kernel (qdc_spec.hpp, qdc_jit.hpp spec_kind).  Circuit::build_program selects a row
+// generic kernel (qdc_spec.hpp, qdc_jit.hpp spec_kind).  Circuit::emit_rq_pass selects a row
 // per pass (rq_select) and plans and generates from it, Circuit::launch_rq launches from it,
 // and the host-only hooks (qdc_rq_variant, qdc_spec_selftest) read the same rows: a kernel is
 // never launched with the block size, slots or grid of another.

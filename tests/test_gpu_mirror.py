@@ -2,7 +2,7 @@
 
 With QDC_MIRROR the forward is scheduled so that its fused passes, run in reverse, are the
 backward's passes, and each backward stage uncomputes with exactly the adjoint of the stage
-matrix the forward applied (qdc_circuit.hpp mirror_schedule / build_program).  The uncompute then
+matrix the forward applied (qdc_circuit.hpp mirror_schedule / mirror_adjoint).  The uncompute then
 drifts like the reference's gate-by-gate U, U^dagger pairs (src/circuit.rs:266-429) instead of
 accumulating the rounding of independently formed forward and reverse stage products.
 QDC_MIRROR=2 makes a backward that cannot mirror its forward an error, so these tests prove the

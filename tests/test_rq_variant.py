@@ -1,6 +1,6 @@
 """The register-resident kernel variants (csrc/qdc_variant.hpp) on CPU: the table of the kernels
 the runtime can launch and the one selector that maps a pass (state count, tile size) and the
-QDC_RW / QDC_RQ_PF / QDC_RQ_SLOTS5 / QDC_MIRROR knobs to a row.  build_program plans and
+QDC_RW / QDC_RQ_PF / QDC_RQ_SLOTS5 / QDC_MIRROR knobs to a row.  emit_rq_pass plans and
 specializes a pass from its row and launch_rq launches it with the row's block size, so a wrong
 row is a kernel started with the wrong number of threads for its LDS and register layout: the
 rows and the selection rules are written out here, independently of the code.  The hook
