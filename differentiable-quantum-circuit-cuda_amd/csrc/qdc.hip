@@ -460,16 +460,17 @@ QDC_API size_t qdc_fusion_schedule(size_t local_qubits, int backward, size_t fir
                              max_ops > 0 ? (uint32_t)std::min(max_ops, qdc::FMAX_OPS)
                                          : (uint32_t)qdc::FMAX_OPS,
                              lcmin > 0 ? (uint32_t)lcmin : 3u};
-  if (const char* e = getenv("QDC_TILE2_CHUNKS")) P.tile2_chunks = (uint32_t)atoi(e);
-  if (const char* e = getenv("QDC_TILE1_CHUNKS")) P.tile1_chunks = (uint32_t)atoi(e);
-  // the runtime's f32 register-resident settings (qdc_circuit.hpp planner())
-  if (const char* e = getenv("QDC_SCHED_RQ")) P.permute = P.rq_grad = atoi(e) != 0;
-  if (const char* e = getenv("QDC_SCHED_PERM")) P.permute = atoi(e) != 0;  // f64: rq_grad only
-  if (const char* e = getenv("QDC_SCHED_MIRROR")) P.mirror = atoi(e) != 0;  // QDC_MIRROR's forward
-  if (const char* e = getenv("QDC_DEFER_Q1")) P.defer_q1 = atoi(e) != 0;
-  if (const char* e = getenv("QDC_RQ_PERM_LOW")) P.perm_low = (uint32_t)atoi(e);
-  if (const char* e = getenv("QDC_RQ_GSTAGE")) P.gamma_stage_cap = atoi(e) != 0;
-  if (const char* e = getenv("QDC_DENS_SPLIT")) P.split_dens = atoi(e) != 0;
+  using qdc::Knob;
+  P.tile2_chunks = qdc::knob_uint(Knob::TILE2_CHUNKS, P.tile2_chunks);
+  P.tile1_chunks = qdc::knob_uint(Knob::TILE1_CHUNKS, P.tile1_chunks);  // (not validated here)
+  // the runtime's f32 register-resident settings (qdc_circuit.hpp planner()): off unless asked for
+  P.permute = P.rq_grad = qdc::knob_int(Knob::SCHED_RQ, 0) != 0;
+  P.permute = qdc::knob_int(Knob::SCHED_PERM, P.permute) != 0;  // f64: rq_grad only
+  P.mirror = qdc::knob_int(Knob::SCHED_MIRROR, P.mirror) != 0;  // QDC_MIRROR's forward
+  P.defer_q1 = qdc::knob_int(Knob::DEFER_Q1, P.defer_q1) != 0;
+  P.perm_low = qdc::knob_uint(Knob::RQ_PERM_LOW, P.perm_low);
+  P.gamma_stage_cap = qdc::knob_int(Knob::RQ_GSTAGE, P.gamma_stage_cap) != 0;
+  P.split_dens = qdc::knob_int(Knob::DENS_SPLIT, P.split_dens) != 0;
   std::vector<qdc_plan_op> pl(plan, plan + n_plan);
   const std::vector<qdc::FusionItem> items = P.fuse_items(pl, backward != 0, first_inject);
   size_t ns = 0, no = 0;
@@ -671,7 +672,7 @@ QDC_API const char* qdc_precompile(size_t n, int world, const int* kinds, const 
   if (kernels) *kernels = names.size();
   // (QDC_PRECOMPILE_DUMP=dir: also write each kernel's source to dir/<name>.hip, in launch order
   // of first use, with dir/order.txt — the per-pass time model joins them with a kernel trace)
-  if (const char* dd = getenv("QDC_PRECOMPILE_DUMP")) {
+  if (const char* dd = qdc::knob_text(qdc::Knob::PRECOMPILE_DUMP)) {
     const std::string d(dd);
     FILE* lst = fopen((d + "/order.txt").c_str(), "a");
     for (size_t i = 0; i < names.size(); ++i) {
@@ -684,8 +685,7 @@ QDC_API const char* qdc_precompile(size_t n, int world, const int* kinds, const 
     if (lst) fclose(lst);
   }
   // (QDC_PRECOMPILE_COUNT=1: count the kernels only)
-  const char* co = getenv("QDC_PRECOMPILE_COUNT");
-  if (names.empty() || (co && atoi(co) != 0)) return nullptr;
+  if (names.empty() || qdc::knob_int(qdc::Knob::PRECOMPILE_COUNT, 0) != 0) return nullptr;
   return qdc::SpecJit::get().compile_only(names, srcs);
 }
 
@@ -819,6 +819,28 @@ QDC_API const char* qdc_rq_variant(int two, unsigned tile_bits, unsigned* out, c
   return nullptr;
 }
 
+// Host-only hook of the knob table (qdc_knobs.hpp): one line per row, name \t scope \t default
+// \t effective value \t effect.  The effective value of a Context / Circuit row is what a
+// default-constructed Ctx::Knobs / Circuit::Knobs holds after read() under the current
+// environment (no device, no circuit); empty for the other scopes.  Writes at most cap bytes
+// (NUL-ended when they fit), returns the bytes needed.
+QDC_API size_t qdc_knob_table(char* out, size_t cap) {
+  std::string value[qdc::KNOB_COUNT];
+  qdc::Ctx::Knobs ck;
+  ck.read();
+  qdc::Ctx::Knobs::each(ck, qdc::KnobShow{value});
+  qdc::Circuit::Knobs rk;
+  if (!rk.read()) qdc::Circuit::Knobs::each(rk, qdc::KnobShow{value});  // (invalid: left empty)
+  std::string t;
+  for (size_t i = 0; i < qdc::KNOB_COUNT; ++i) {
+    const qdc::KnobRow& r = qdc::KNOB_TABLE[i];
+    t += std::string(r.name) + "\t" + qdc::knob_scope_name(r.scope) + "\t" + r.dflt + "\t" +
+         value[i] + "\t" + r.effect + "\n";
+  }
+  if (out && cap > 0) std::memcpy(out, t.c_str(), std::min(cap, t.size() + 1));
+  return t.size() + 1;
+}
+
 QDC_API size_t qdc_rq_plan(unsigned tile_bits, unsigned slots, const unsigned* kinds,
                            const unsigned* t1, const unsigned* t2,
                            const unsigned long long* deps, size_t n, unsigned* steps,
@@ -827,10 +849,11 @@ QDC_API size_t qdc_rq_plan(unsigned tile_bits, unsigned slots, const unsigned* k
   if (slots != 4 && slots != 5) return SIZE_MAX;
   std::vector<qdc::RqStage> st(n);
   for (size_t i = 0; i < n; ++i) st[i] = qdc::RqStage{kinds[i], t1[i], t2[i], deps ? deps[i] : 0};
-  const char* mc = getenv("QDC_RQ_MAXCL");  // the runtime's knob (qdc_circuit.hpp)
-  const char* kp = getenv("QDC_RQ_KEEP");  // (tests: the half-buffer planning, rq_plan keep)
-  const qdc::RqPlan plan = qdc::rq_plan(st, tile_bits, nullptr, !(mc && atoi(mc) == 0), slots,
-                                        kp && atoi(kp) != 0);
+  // QDC_RQ_MAXCL: the runtime's knob (qdc_circuit.hpp); QDC_RQ_KEEP (tests): the half-buffer
+  // planning, rq_plan keep
+  const qdc::RqPlan plan =
+      qdc::rq_plan(st, tile_bits, nullptr, qdc::knob_int(qdc::Knob::RQ_MAXCL, 1) != 0, slots,
+                   qdc::knob_int(qdc::Knob::RQ_KEEP, 0) != 0);
   if (plan.steps.size() + 2 > cap) return SIZE_MAX;
   auto put = [&](size_t i, unsigned kind, unsigned stage, unsigned cs, const qdc::RqLayout& L) {
     unsigned* o = steps + 8 * i;

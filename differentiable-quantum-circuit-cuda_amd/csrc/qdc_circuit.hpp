@@ -236,13 +236,131 @@ struct Circuit {
   cx* host_out = nullptr;  // pinned
   size_t host_cap = 0;
   std::vector<Instr> ins;
-  // fused multi-gate passes
-  int fuse = 1;             // 0: one HBM pass per gate
-  uint32_t fuse_max_ops = FMAX_OPS;
-  uint32_t fuse_lcmin = 3;  // min contiguous chunk bits of a fused tile (128-B rows)
-  int fuse_meas = 1;        // densities / cotangent injections join fused passes
-  int use_rq = 1;           // f32 gate passes run register-resident (qdc_rq.hpp)
-  int rq_stats = 0;
+  // The circuit's QDC_* knobs (qdc_knobs.hpp, scope Circuit): read() fills them from the
+  // environment when a circuit is created, dry circuits included; host only.
+  struct Knobs {
+    // fused multi-gate passes
+    int fuse = 1;             // 0: one HBM pass per gate
+    uint32_t fuse_max_ops = FMAX_OPS;
+    uint32_t fuse_lcmin = 3;  // min contiguous chunk bits of a fused tile (128-B rows)
+    int fuse_meas = 1;        // densities / cotangent injections join fused passes
+    int use_rq = 1;           // f32 gate passes run register-resident (qdc_rq.hpp)
+    int rq_stats = 0;
+    // which register-resident kernel variant runs a pass (QDC_RW, QDC_RQ_PF, QDC_RQ_SLOTS5): read
+    // by rq_variant() below and nowhere else
+    RqKnobs rqk;
+    int rq64 = 1;  // f64 gate passes register-resident too (k_rw; QDC_RQ64)
+    // register-resident tile order: 0 block-contiguous, 1 grid-strided, 2 block-contiguous in
+    // XCD-aware block order (QDC_RQ_ORDER).  C2 n = 28, same box (profiles/r5/r5q_*): 2 is
+    // +0.4-0.6 % over 0, 1 (concurrent tiles neighbours in memory) -6.5 %
+    int rq_order = 2;
+    // register-resident passes as straight-line kernels specialized per pass program
+    // (qdc_spec.hpp, qdc_jit.hpp; QDC_SPEC): 0 off, 1 for states of >= spec_min_qubits local
+    // qubits, 2 always; a call whose program needs more than spec_max distinct kernels runs generic
+    int spec_mode = 1;
+    uint32_t spec_min_qubits = 22;
+    uint32_t spec_max = 160;
+    int spec_fwd = 1;  // forward (one-state) passes too (QDC_SPEC_FWD)
+    // a program with more than spec_max distinct kernels: its missing kernels are compiled by the
+    // JIT's background thread while the generic kernels run its passes, later calls launch the
+    // specialized ones as their objects appear (QDC_SPEC_ASYNC=0: such programs stay generic).
+    // f32 only by default: f32 specialized and generic passes are bit-identical, so a result never
+    // depends on how far the background compiler has got; f64 ones differ in the last bits (the
+    // compiler contracts the scalar complex arithmetic differently), so a deep f64 program stays
+    // generic — reproducible from call to call — unless QDC_SPEC_ASYNC=1 opts in
+    int spec_async = sizeof(real) == 4 ? 1 : 0;
+    int rq_permute = 1;      // gate-only passes permute their tile's qubits (QDC_RQ_PERM)
+    int rq_perm_shard = 1;    // ... on sharded circuits too (QDC_RQ_PERM_SHARD)
+    int rq_grad32 = 1;        // two-state passes hold up to FMAX_GRAD_RQ Gamma stages (QDC_RQ_GRAD32)
+    int rq_maxcl = 1;         // relayouts chosen by max closure, else greedily (QDC_RQ_MAXCL)
+    uint32_t rq_perm_low = 0;  // low positions a permuting pass fills, 0: default (QDC_RQ_PERM_LOW)
+    int rq_gstage = 1;  // two-state passes capped by Gamma stages, not variable gates (QDC_RQ_GSTAGE)
+    // one-state fused tile in chunks (QDC_TILE1_CHUNKS): TILE_CHUNKS_1, or TILE_CHUNKS_2 (f32:
+    // 2^11 amplitudes; the kernels of either size: qdc_variant.hpp)
+    uint32_t tile1_chunks = FusionPlanner::TILE_CHUNKS_1;
+    // runs of cotangent injections whose cotangents are all diagonal become one elementwise pass
+    // (k_diag_inject; QDC_DIAG_INJECT)
+    int diag_inject = 1;
+    // the backward's leading diagonal-injection passes launched before its program is built
+    // (QDC_EARLY_INJECT)
+    int early_inject = 1;
+    // read-only passes of one-qubit densities on k_dens1 (register partial sums across a block's
+    // tiles, one reduction per block; QDC_DENS1=0: k_fused's per-tile reductions)
+    int dens1_kernel = 1;
+    int dens_split = 1;  // forward passes hold gates or densities, not both (qdc_fusion.hpp split_dens)
+    // Mirrored schedules (QDC_MIRROR): the forward is scheduled on the two-state tile under both
+    // directions' rules (qdc_fusion.hpp FusionPlanner::mirror) and the backward runs its passes in
+    // reverse, uncomputing each stage with exactly the adjoint of the matrix the forward applied —
+    // the O(1)-memory uncompute then drifts like the reference's gate-by-gate U, U^dagger sequence
+    // instead of accumulating the rounding of independently formed stage products.  Sharded
+    // circuits too (round 5): the forward's remap plan keeps both directions' order relations and
+    // the backward undoes its remaps in reverse (unremap).  The backward must follow a forward call
+    // with the same gates (else the backward schedules itself as usual).  On by default (round
+    // 4: C5 n = 14 f32 uncompute 4.85x -> 1.4x the reference's floor; C2 n = 28 f32 ~3.5 %
+    // slower, DESIGN.md "Uncompute drift").
+    int mirror = 1;
+    // one-state one-wave specialized passes relayout through half the LDS buffer when every
+    // relayout keeps a register slot (QDC_SPEC_HALF; twice the resident waves)
+    int spec_half = 1;
+    // trailing one-qubit stages of a pass join their qubit's next two-qubit stage in a later pass
+    // (qdc_fusion.hpp defer_trailing_q1; QDC_DEFER_Q1)
+    int defer_q1 = 1;
+    // grid of fused passes (QDC_FUSED_BLOCKS); 0: as many blocks as are resident at once
+    // (occupancy query)
+    uint32_t fused_blocks = 0;
+    // the pass schedule of a call is reused by the next call with the same plan (sched_cache;
+    // QDC_SCHED_CACHE)
+    int sched_cache_on = 1;
+    // the forward and cotangent states interleaved in one allocation, in blocks of
+    // 2^state_ilv_bits chunks (alloc_pair; QDC_STATE_ILV, QDC_STATE_ILV_BITS)
+    int state_ilv = 1;
+    uint32_t state_ilv_bits = 12;
+
+    template <class K, class F>
+    static void each(K& k, F&& f) {
+      f(Knob::FUSE, k.fuse);
+      f(Knob::FUSE_MAX_OPS, k.fuse_max_ops, 1, FMAX_OPS);
+      f(Knob::FUSE_MEAS, k.fuse_meas);
+      f(Knob::FUSE_LCMIN, k.fuse_lcmin, 1, LOWBITS);
+      f(Knob::FUSED_BLOCKS, k.fused_blocks, 1, (int)NBMAX);
+      f(Knob::RQ, k.use_rq);
+      f(Knob::RQ64, k.rq64);
+      f(Knob::RQ_STATS, k.rq_stats);
+      f(Knob::RW, k.rqk.rq_wave);
+      f(Knob::RQ_PF, k.rqk.rq_prefetch);
+      f(Knob::RQ_SLOTS5, k.rqk.rq_slots5);
+      f(Knob::RQ_ORDER, k.rq_order);
+      f(Knob::RQ_PERM, k.rq_permute);
+      f(Knob::RQ_PERM_SHARD, k.rq_perm_shard);
+      f(Knob::RQ_PERM_LOW, k.rq_perm_low);
+      f(Knob::RQ_GRAD32, k.rq_grad32);
+      f(Knob::RQ_MAXCL, k.rq_maxcl);
+      f(Knob::RQ_GSTAGE, k.rq_gstage);
+      f(Knob::TILE1_CHUNKS, k.tile1_chunks);
+      f(Knob::DIAG_INJECT, k.diag_inject);
+      f(Knob::EARLY_INJECT, k.early_inject);
+      f(Knob::DENS1, k.dens1_kernel);
+      f(Knob::DENS_SPLIT, k.dens_split);
+      f(Knob::MIRROR, k.mirror);
+      f(Knob::DEFER_Q1, k.defer_q1);
+      f(Knob::SCHED_CACHE, k.sched_cache_on);
+      f(Knob::SPEC, k.spec_mode);
+      f(Knob::SPEC_MIN_QUBITS, k.spec_min_qubits);
+      f(Knob::SPEC_MAX, k.spec_max);
+      f(Knob::SPEC_FWD, k.spec_fwd);
+      f(Knob::SPEC_ASYNC, k.spec_async);
+      f(Knob::SPEC_HALF, k.spec_half);
+      f(Knob::STATE_ILV, k.state_ilv);
+      f(Knob::STATE_ILV_BITS, k.state_ilv_bits, 4, 24);
+    }
+    const char* read() {
+      each(*this, KnobRead{});
+      constexpr uint32_t T1 = FusionPlanner::TILE_CHUNKS_1, T2 = FusionPlanner::TILE_CHUNKS_2;
+      if (tile1_chunks != T1 && tile1_chunks != T2)
+        return fail("%s must be %u or %u", KNOB_TABLE[(int)Knob::TILE1_CHUNKS].name, T1, T2);
+      return nullptr;
+    }
+  } k;
   // host time of the calls (qdc_circuit_host_times): per direction (0 run/forward, 1 backward)
   // the calls and the milliseconds of setup, scheduling, program build, launching and the
   // finish (stream sync and result copies), accumulated since the last reset
@@ -255,74 +373,16 @@ struct Circuit {
     host_ms[dir][0] += 1;
     for (int k = 1; k < 6; ++k) host_ms[dir][k] += ms_between(t[k - 1], t[k]);
   }
-  // which register-resident kernel variant runs a pass (QDC_RW, QDC_RQ_PF, QDC_RQ_SLOTS5): read
-  // by rq_variant() below and nowhere else
-  RqKnobs rqk;
-  int rq64 = 1;  // f64 gate passes register-resident too (k_rw; QDC_RQ64)
-  // register-resident tile order: 0 block-contiguous, 1 grid-strided, 2 block-contiguous in
-  // XCD-aware block order (QDC_RQ_ORDER).  C2 n = 28, same box (profiles/r5/r5q_*): 2 is
-  // +0.4-0.6 % over 0, 1 (concurrent tiles neighbours in memory) -6.5 %
-  int rq_order = 2;
-  // register-resident passes as straight-line kernels specialized per pass program
-  // (qdc_spec.hpp, qdc_jit.hpp; QDC_SPEC): 0 off, 1 for states of >= spec_min_qubits local
-  // qubits, 2 always; a call whose program needs more than spec_max distinct kernels runs generic
-  int spec_mode = 1;
-  uint32_t spec_min_qubits = 22;
-  uint32_t spec_max = 160;
-  int spec_fwd = 1;  // forward (one-state) passes too (QDC_SPEC_FWD)
-  // a program with more than spec_max distinct kernels: its missing kernels are compiled by the
-  // JIT's background thread while the generic kernels run its passes, later calls launch the
-  // specialized ones as their objects appear (QDC_SPEC_ASYNC=0: such programs stay generic).
-  // f32 only by default: f32 specialized and generic passes are bit-identical, so a result never
-  // depends on how far the background compiler has got; f64 ones differ in the last bits (the
-  // compiler contracts the scalar complex arithmetic differently), so a deep f64 program stays
-  // generic — reproducible from call to call — unless QDC_SPEC_ASYNC=1 opts in
-  int spec_async = sizeof(real) == 4 ? 1 : 0;
   // generated kernels by pass program (key: spec_entry), with their functions
   std::map<std::vector<uint32_t>, SpecEntry> spec_cache;
   uint64_t spec_epoch = 0;
-  int rq_permute = 1;      // gate-only passes permute their tile's qubits (QDC_RQ_PERM)
-  int rq_perm_shard = 1;    // ... on sharded circuits too (QDC_RQ_PERM_SHARD)
-  int rq_grad32 = 1;        // two-state passes hold up to FMAX_GRAD_RQ Gamma stages (QDC_RQ_GRAD32)
-  int rq_maxcl = 1;         // relayouts chosen by max closure, else greedily (QDC_RQ_MAXCL)
-  uint32_t rq_perm_low = 0;  // low positions a permuting pass fills, 0: default (QDC_RQ_PERM_LOW)
-  int rq_gstage = 1;  // two-state passes capped by Gamma stages, not variable gates (QDC_RQ_GSTAGE)
-  // one-state fused tile in chunks (QDC_TILE1_CHUNKS): TILE_CHUNKS_1, or TILE_CHUNKS_2 (f32: 2^11
-  // amplitudes; the kernels of either size: qdc_variant.hpp)
-  uint32_t tile1_chunks = TILE_CHUNKS_1;
-  // runs of cotangent injections whose cotangents are all diagonal become one elementwise pass
-  // (k_diag_inject; QDC_DIAG_INJECT)
-  int diag_inject = 1;
-  // the backward's leading diagonal-injection passes launched before its program is built
-  // (QDC_EARLY_INJECT)
-  int early_inject = 1;
-  // read-only passes of one-qubit densities on k_dens1 (register partial sums across a block's
-  // tiles, one reduction per block; QDC_DENS1=0: k_fused's per-tile reductions)
-  int dens1_kernel = 1;
-  int dens_split = 1;  // forward passes hold gates or densities, not both (qdc_fusion.hpp split_dens)
-  // Mirrored schedules (QDC_MIRROR): the forward is scheduled on the two-state tile under both
-  // directions' rules (qdc_fusion.hpp FusionPlanner::mirror) and the backward runs its passes in
-  // reverse, uncomputing each stage with exactly the adjoint of the matrix the forward applied —
-  // the O(1)-memory uncompute then drifts like the reference's gate-by-gate U, U^dagger sequence
-  // instead of accumulating the rounding of independently formed stage products.  Sharded
-  // circuits too (round 5): the forward's remap plan keeps both directions' order relations and
-  // the backward undoes its remaps in reverse (unremap).  The backward must follow a forward call
-  // with the same gates (else the backward schedules itself as usual).  On by default (round 4: C5 n = 14 f32 uncompute 4.85x -> 1.4x
-  // the reference's floor; C2 n = 28 f32 ~3.5 % slower, DESIGN.md "Uncompute drift").
-  int mirror = 1;
-  // one-state one-wave specialized passes relayout through half the LDS buffer when every
-  // relayout keeps a register slot (QDC_SPEC_HALF; twice the resident waves)
-  int spec_half = 1;
-  // trailing one-qubit stages of a pass join their qubit's next two-qubit stage in a later pass
-  // (qdc_fusion.hpp defer_trailing_q1; QDC_DEFER_Q1)
-  int defer_q1 = 1;
   bool mirror_on() const {
-    return mirror && fuse && fuse_max_ops >= 2 && use_rq && (sizeof(real) == 4 || rq64);
+    return k.mirror && k.fuse && k.fuse_max_ops >= 2 && k.use_rq && (sizeof(real) == 4 || k.rq64);
   }
   // The kernel variant (qdc_variant.hpp) of a register-resident pass on 2^tbits-amplitude tiles:
   // the one selection that planning (emit_rq_pass), specialization and launch (launch_rq) share
   const char* rq_variant(bool two, uint32_t tbits, const RqVariant*& V) const {
-    V = rq_select(two, tbits, rqk, mirror_on());
+    V = rq_select(two, tbits, k.rqk, mirror_on());
     if (!V)
       return fail("no register-resident kernel for a %u-amplitude %s tile", 1u << tbits,
                   two ? "two-state" : "one-state");
@@ -330,7 +390,7 @@ struct Circuit {
   }
   // its five-slot passes (2^11 tiles) are planned to keep a slot in place across every relayout
   // where they can, for the half-buffer specialized form (rq_plan keep)
-  bool rq_keep(const RqVariant& V) const { return spec_half && V.ns == 5; }
+  bool rq_keep(const RqVariant& V) const { return k.spec_half && V.ns == 5; }
 
   // host-only dry run (init_dry): calls stop before their first launch; build_program writes
   // the pass program into dry_prog and collects the specialized kernels into dry_specs
@@ -349,7 +409,6 @@ struct Circuit {
   std::vector<TraceOp> trace;
   size_t trace_from = 0;
   std::vector<uint8_t> inexact;  // per instruction: gate not unitary to working precision
-  uint32_t fused_blocks = 0;  // 0: as many blocks as are resident at once (occupancy query)
   std::vector<std::pair<const void*, uint32_t>> fused_resident_cache;
   uint32_t last_fused_grid = 0;
   uint32_t last_fused_ndyn = 0;  // granule partials per slot of the last fused launch
@@ -431,49 +490,9 @@ struct Circuit {
   }
   // the runtime's QDC_* knobs (environment, read once per circuit)
   const char* read_knobs(int world, int nlocal) {
-    if (const char* e = getenv("QDC_FUSE")) fuse = atoi(e);
-    if (const char* e = getenv("QDC_FUSE_MAX_OPS"))
-      fuse_max_ops = std::max(1, std::min(atoi(e), FMAX_OPS));
-    if (const char* e = getenv("QDC_FUSE_MEAS")) fuse_meas = atoi(e);
-    if (const char* e = getenv("QDC_RQ")) use_rq = atoi(e);
-    if (const char* e = getenv("QDC_RQ_STATS")) rq_stats = atoi(e);
-    if (const char* e = getenv("QDC_RQ_PF")) rqk.rq_prefetch = atoi(e);
-    if (const char* e = getenv("QDC_RW")) rqk.rq_wave = atoi(e);
-    if (const char* e = getenv("QDC_RQ_ORDER")) rq_order = atoi(e);
-    if (const char* e = getenv("QDC_RQ64")) rq64 = atoi(e);
-    if (const char* e = getenv("QDC_RQ_SLOTS5")) rqk.rq_slots5 = atoi(e);
-    if (const char* e = getenv("QDC_RQ_PERM")) rq_permute = atoi(e);
-    if (const char* e = getenv("QDC_RQ_PERM_SHARD")) rq_perm_shard = atoi(e);
-    if (const char* e = getenv("QDC_RQ_GRAD32")) rq_grad32 = atoi(e);
-    if (const char* e = getenv("QDC_RQ_MAXCL")) rq_maxcl = atoi(e);
-    if (const char* e = getenv("QDC_RQ_PERM_LOW")) rq_perm_low = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_RQ_GSTAGE")) rq_gstage = atoi(e);
-    if (const char* e = getenv("QDC_DIAG_INJECT")) diag_inject = atoi(e);
-    if (const char* e = getenv("QDC_EARLY_INJECT")) early_inject = atoi(e);
-    if (const char* e = getenv("QDC_DENS1")) dens1_kernel = atoi(e);
-    if (const char* e = getenv("QDC_DENS_SPLIT")) dens_split = atoi(e);
-    if (const char* e = getenv("QDC_MIRROR")) mirror = atoi(e);
-    if (const char* e = getenv("QDC_SPEC_HALF")) spec_half = atoi(e);
-    if (const char* e = getenv("QDC_DEFER_Q1")) defer_q1 = atoi(e);
-    if (const char* e = getenv("QDC_SCHED_CACHE")) sched_cache_on = atoi(e);
-    if (const char* e = getenv("QDC_TILE1_CHUNKS")) {
-      const uint32_t t = (uint32_t)atoi(e);
-      if (t != TILE_CHUNKS_1 && t != TILE_CHUNKS_2)
-        return fail("QDC_TILE1_CHUNKS must be %u or %u", TILE_CHUNKS_1, TILE_CHUNKS_2);
-      tile1_chunks = t;
-    }
-    if (const char* e = getenv("QDC_SPEC")) spec_mode = atoi(e);
-    if (const char* e = getenv("QDC_SPEC_MIN_QUBITS")) spec_min_qubits = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_SPEC_MAX")) spec_max = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_SPEC_FWD")) spec_fwd = atoi(e);
-    if (const char* e = getenv("QDC_SPEC_ASYNC")) spec_async = atoi(e);
+    QDC_TRY(k.read());
     // the node's hipcc processes shared among the ranks of a multi-process job
     SpecJit::get().set_processes(std::max(1, world / std::max(1, nlocal)));
-
-    if (const char* e = getenv("QDC_FUSE_LCMIN"))
-      fuse_lcmin = (uint32_t)std::max(1, std::min(atoi(e), LOWBITS));
-    if (const char* e = getenv("QDC_FUSED_BLOCKS"))
-      fused_blocks = (uint32_t)std::max(1, std::min(atoi(e), (int)NBMAX));
     return nullptr;
   }
   // A host-only circuit (no device, no state): plans, schedules and pass programs exactly as
@@ -520,11 +539,9 @@ struct Circuit {
   // allocated on the first backward).  The initial copy, the bwd zeroing and every gate-shaped
   // kernel address the pair through Ctx::gm; readbacks copy block by block (read_state).
   const char* alloc_pair(Shard& s, size_t bytes) {
-    const char* e = getenv("QDC_STATE_ILV");
     // block size: 2^12 chunks (QDC_STATE_ILV_BITS); states of at least two blocks
-    uint32_t gb = 12;
-    if (const char* b = getenv("QDC_STATE_ILV_BITS")) gb = (uint32_t)std::max(4, std::min(atoi(b), 24));
-    bool ilv = !(e && atoi(e) == 0) && g == 0 && sh.size() == 1 &&
+    const uint32_t gb = k.state_ilv_bits;
+    bool ilv = k.state_ilv != 0 && g == 0 && sh.size() == 1 &&
                nchunks_of(nl) >= ((uint64_t)2 << gb);
     if (ilv) {
       // the pair allocates bwd now, not on the first backward (circuit.rs:276 creates it
@@ -920,19 +937,19 @@ struct Circuit {
   static constexpr uint32_t TILE_CHUNKS_1 = FusionPlanner::TILE_CHUNKS_1;
   static constexpr uint32_t TILE_CHUNKS_2 = FusionPlanner::TILE_CHUNKS_2;
   FusionPlanner planner() const {
-    FusionPlanner P{ins, inexact, nl, fuse != 0, fuse_meas != 0, fuse_max_ops, fuse_lcmin};
+    FusionPlanner P{ins, inexact, nl, k.fuse != 0, k.fuse_meas != 0, k.fuse_max_ops, k.fuse_lcmin};
     // gate-only passes permute their tile on the way out when they are register-resident
     // (sharded circuits too, round 5: later remaps' victims are relabelled, qdc_fusion.hpp
     // relabel_remap; QDC_RQ_PERM_SHARD=0 keeps their layouts fixed)
-    P.permute = rq_permute && use_rq && (g == 0 || rq_perm_shard) && sizeof(real) == 4;
+    P.permute = k.rq_permute && k.use_rq && (g == 0 || k.rq_perm_shard) && sizeof(real) == 4;
     P.ng = g;
-    P.rq_grad = rq_grad32 && use_rq && (sizeof(real) == 4 || rq64);
-    if (rq_perm_low) P.perm_low = rq_perm_low;
-    P.tile1_chunks = tile1_chunks;
+    P.rq_grad = k.rq_grad32 && k.use_rq && (sizeof(real) == 4 || k.rq64);
+    if (k.rq_perm_low) P.perm_low = k.rq_perm_low;
+    P.tile1_chunks = k.tile1_chunks;
     P.mirror = mirror_on() && sched_mirror;
-    P.defer_q1 = defer_q1 != 0;
-    P.gamma_stage_cap = rq_gstage != 0;
-    P.split_dens = dens_split != 0;
+    P.defer_q1 = k.defer_q1 != 0;
+    P.gamma_stage_cap = k.rq_gstage != 0;
+    P.split_dens = k.dens_split != 0;
     return P;
   }
   bool is_meas(const qdc_plan_op& op) const { return planner().is_meas(op); }
@@ -962,7 +979,6 @@ struct Circuit {
   // the schedule being built is a mirrored forward's (forward calls only: a run call has no
   // backward to mirror and keeps the one-state schedule)
   bool sched_mirror = false;
-  int sched_cache_on = 1;
   static bool same_plan(const std::vector<qdc_plan_op>& a, const std::vector<qdc_plan_op>& b) {
     if (a.size() != b.size()) return false;
     for (size_t i = 0; i < a.size(); ++i) {
@@ -977,7 +993,7 @@ struct Circuit {
   }
   std::vector<Item> schedule(std::vector<qdc_plan_op>& plan, bool backward, size_t first_inject) {
     SchedCache& c = sched_cache[backward ? 1 : 0];
-    if (sched_cache_on && c.valid && c.first_inject == first_inject && c.inexact == inexact &&
+    if (k.sched_cache_on && c.valid && c.first_inject == first_inject && c.inexact == inexact &&
         c.mirror == sched_mirror && same_plan(c.in_plan, plan)) {
       plan = c.out_plan;
       return c.items;
@@ -985,7 +1001,7 @@ struct Circuit {
     c.valid = false;
     c.in_plan = plan;
     std::vector<Item> items = fuse_items(plan, backward, first_inject);
-    if (sched_cache_on) {
+    if (k.sched_cache_on) {
       c.out_plan = plan;
       c.items = items;
       c.inexact = inexact;
@@ -1098,10 +1114,10 @@ struct Circuit {
     Build B{plan, backward, first_inject, cg, vg, gidx, var_idx, out_idx, dg,
             reinterpret_cast<fop*>(prog_host), reinterpret_cast<cx*>(prog_host + mats_off), 0, 0,
             nvar, {}, {}, {}, {}, {}};
-    B.ops.reserve(fuse_max_ops);
-    B.gates.reserve(fuse_max_ops);
-    B.rs.reserve(fuse_max_ops);
-    B.sst.reserve(2 * (size_t)fuse_max_ops + 1);
+    B.ops.reserve(k.fuse_max_ops);
+    B.gates.reserve(k.fuse_max_ops);
+    B.rs.reserve(k.fuse_max_ops);
+    B.sst.reserve(2 * (size_t)k.fuse_max_ops + 1);
     for (size_t ii = 0; ii < items.size(); ++ii) {
       Item& it = items[ii];
       if (it.type != 2) continue;
@@ -1322,7 +1338,7 @@ struct Circuit {
   // injections), f32 or rq64; else the LDS kernel, or k_dens1 for a read-only pass of one-qubit
   // densities.
   const char* classify_pass(const Build& B, Item& it, bool two) const {
-    bool rq = use_rq && (sizeof(real) == 4 || rq64) && it.writes_f;
+    bool rq = k.use_rq && (sizeof(real) == 4 || k.rq64) && it.writes_f;
     for (const StageOp& o : B.ops) rq = rq && (o.F.kind & 7u) <= FK_DIAG;
     it.rq = rq;
     if (!it.swaps.empty() && !rq)
@@ -1335,7 +1351,7 @@ struct Circuit {
     if (nred > cap)
       return fail("internal: a fused pass has %zu reduction ops, the kernel holds %zu", nred, cap);
     if (rq) return nullptr;
-    bool d1 = dens1_kernel && !two && !it.writes_f && !B.ops.empty() && B.ops.size() <= (size_t)DENS1_MAX;
+    bool d1 = k.dens1_kernel && !two && !it.writes_f && !B.ops.empty() && B.ops.size() <= (size_t)DENS1_MAX;
     for (const StageOp& o : B.ops) d1 = d1 && (o.F.kind & 7u) == FK_DENS1;
     it.dens1 = d1;
     return nullptr;
@@ -1379,7 +1395,7 @@ struct Circuit {
     // the kernel variant that will run the pass: the plan's register slots come from it
     QDC_TRY(rq_variant(two, it.tbits, it.var));
     const RqVariant& V = *it.var;
-    const RqPlan& P = rq_plan_cached(B.rs, it.tbits, perm ? src : nullptr, rq_maxcl != 0, V.ns,
+    const RqPlan& P = rq_plan_cached(B.rs, it.tbits, perm ? src : nullptr, k.rq_maxcl != 0, V.ns,
                                      rq_keep(V));
     it.l0 = put_layout(B, P.load, it.tbits);
     {  // rqio after the load descriptor
@@ -1398,7 +1414,7 @@ struct Circuit {
     uint32_t nfop = 0;
     it.grad_slots.clear();  // the kernel reduces Gamma stages in execution order
     // the variant's specialized pass (one-state passes: QDC_SPEC_FWD)
-    const bool spec = V.prefix && spec_on() && (two || spec_fwd);
+    const bool spec = V.prefix && spec_on() && (two || k.spec_fwd);
     B.sst.clear();
     RqLayout lcur = P.load;
     for (const RqStep& step : P.steps) {
@@ -1432,9 +1448,9 @@ struct Circuit {
     }
     it.nstage = nfop;
     it.spec = spec ? spec_entry(B, V, it.tbits, P.load) : nullptr;
-    if (rq_stats)
+    if (k.rq_stats)
       fprintf(stderr, "rq pass: %zu stages, %u ops (T=%u lc=%u)\n", B.ops.size(), nfop, it.tbits, it.lc);
-    if (rq_stats >= 2) {  // the pass's stages for offline planner studies (tools/)
+    if (k.rq_stats >= 2) {  // the pass's stages for offline planner studies (tools/)
       fprintf(stderr, "rq stages %s T=%u perm=%d:", two ? "two" : "one", it.tbits, perm ? 1 : 0);
       for (const RqStage& r : B.rs)
         fprintf(stderr, " %u,%u,%u,%llx", r.kind, r.t1, r.t2, (unsigned long long)r.deps);
@@ -1446,7 +1462,7 @@ struct Circuit {
   // source is generated once per distinct program (per process): the key is everything it
   // depends on, the layouts, stage kinds, slot cases and Gamma flags
   SpecEntry* spec_entry(Build& B, const RqVariant& V, uint32_t tbits, const RqLayout& load) {
-    const bool half = V.pass_half && spec_half && !spec_imm() && spec_half_ok(B.sst);
+    const bool half = V.pass_half && k.spec_half && !spec_imm() && spec_half_ok(B.sst);
     std::vector<uint32_t>& key = B.key;
     key.assign({(uint32_t)(&V - rq_variants()), tbits, spec_imm() ? 1u : 0u, half ? 1u : 0u});
     auto put_layout_key = [&](const RqLayout& L) {
@@ -1477,7 +1493,7 @@ struct Circuit {
   }
   // specialized passes: circuits of >= spec_min_qubits local qubits (every shard runs the same
   // program; the kernels are loaded on each shard's device)
-  bool spec_on() const { return spec_mode > 0 && (spec_mode >= 2 || nl >= spec_min_qubits); }
+  bool spec_on() const { return k.spec_mode > 0 && (k.spec_mode >= 2 || nl >= k.spec_min_qubits); }
   // compile / load the kernels of this program's specialized passes (more distinct ones than
   // spec_max — deep random circuits would compile for minutes — go to the background compiler)
   const char* spec_load(std::vector<Item>& items) {
@@ -1490,8 +1506,8 @@ struct Circuit {
         ++distinct;
       }
     if (distinct == 0) return nullptr;
-    const bool async = distinct > spec_max;
-    if (async && !spec_async) {  // every pass of this call interpreted
+    const bool async = distinct > k.spec_max;
+    if (async && !k.spec_async) {  // every pass of this call interpreted
       for (Item& it : items) it.spec = nullptr;
       return nullptr;
     }
@@ -1621,8 +1637,8 @@ struct Circuit {
   // QDC_FUSED_BLOCKS.  fn: a loaded specialized kernel asked for its own occupancy instead (it
   // may differ from the interpreted kernel's).
   const char* fused_grid(const void* kernel, hipFunction_t fn, int nt, uint32_t& grid) {
-    if (fused_blocks) {
-      grid = fused_blocks;
+    if (k.fused_blocks) {
+      grid = k.fused_blocks;
       return nullptr;
     }
     const void* key = fn ? (const void*)fn : kernel;
@@ -1663,7 +1679,7 @@ struct Circuit {
   // stages, densities) go to slots it.grad_slots of red_base (grads or dens of each shard).
   const char* run_fused(const Item& it, bool two, size_t mats_off, bool red_to_grads) {
     fgeo fg{};
-    fg.order = it.rq ? (uint32_t)rq_order : 0u;
+    fg.order = it.rq ? (uint32_t)k.rq_order : 0u;
     fg.gm = gm;
     fg.lc = it.lc;
     fg.h = it.h;
@@ -1829,7 +1845,7 @@ struct Circuit {
     QDC_TRY(berr);
     ht[3] = hclock::now();
     if (record) mrec.capture(cg, vg, pl, items, std::move(mats_rec), inexact);
-    if (rq_stats)
+    if (k.rq_stats)
       fprintf(stderr, "forward plan+build %.3f ms\n",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count());
     if (dry) {  // the layout the passes leave (permuting passes' swaps, remaps), no launch
@@ -2024,7 +2040,7 @@ struct Circuit {
     pl = plan(QDC_PLAN_BACKWARD);
     first_inject = first_injection(pl);
     // QDC_MIRROR=2 (tests): a backward that cannot mirror its forward is an error
-    if (mirror_on() && mirror == 2)
+    if (mirror_on() && k.mirror == 2)
       return fail("mirror: the backward does not follow a forward call with the same gates");
     items = schedule(pl, true, first_inject);
     return nullptr;
@@ -2065,7 +2081,7 @@ struct Circuit {
     std::vector<Item> items;
     size_t first_inject = 0;
     QDC_TRY(schedule_backward(cg, vg, pl, items, first_inject));
-    if (diag_inject) merge_diag_injections(items, pl, dg, gidx);
+    if (k.diag_inject) merge_diag_injections(items, pl, dg, gidx);
     ht[2] = hclock::now();
     // a run of diagonal cotangent injections: one elementwise pass (no pass program)
     auto run_diag_inject = [&](const Item& item) -> const char* {
@@ -2082,7 +2098,7 @@ struct Circuit {
     // before it is built, so the device runs them during the host's build (round 6;
     // QDC_EARLY_INJECT=0: after)
     size_t lead = 0;
-    if (!dry && early_inject)
+    if (!dry && k.early_inject)
       for (; lead < items.size() && items[lead].type == 3; ++lead) QDC_TRY(run_diag_inject(items[lead]));
     size_t mats_off = 0;
     const auto tb0 = std::chrono::steady_clock::now();
@@ -2090,7 +2106,7 @@ struct Circuit {
                           (uint32_t)nvar, {}, &dg));
     ht[3] = hclock::now();
     if (dry) return tracing ? trace_logical(items, pl, true, cg, vg, gidx) : nullptr;
-    if (rq_stats)
+    if (k.rq_stats)
       fprintf(stderr, "backward plan+build %.3f ms\n",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count());
     for (size_t ii = lead; ii < items.size(); ++ii) {

@@ -21,6 +21,7 @@
 
 #include "qdc/primitives.h"
 #include "qdc_kernels.hpp"
+#include "qdc_knobs.hpp"
 
 namespace qdc {
 
@@ -118,89 +119,134 @@ struct DeviceGuard {
 struct Ctx {
   int device = 0;
   hipStream_t stream = nullptr;
-  uint32_t grid_cap = 1u << 20;  // streaming launches: ~one item per thread (measured best)
-  uint32_t red_cap = 2048;   // target blocks of reduction launches (<= NBMAX)
-  // the same for the single-gate reverse with its gradient (both states read and written; knob
-  // QDC_REV_RED): at 4096 instead of 2048 blocks reverse_q2 +1..2 points at 5 of 7 pairs
-  // ((26,27) 72.4 -> 74.3 %, (0,1) 75.9 -> 77.1 %), reverse_q1 +0.5..1 (profiles/r6/r6m)
-  uint32_t rev_red_cap = NBMAX;
   double next_flops = 0;     // algorithmic FLOPs of the next launch (profiling; reset by launch)
   // gap mask of the states this context's gate-shaped launches address: chunk c of a state at
   // c + (c & gm).  Nonzero for a circuit whose fwd / bwd states are interleaved in one
   // allocation (qdc_circuit.hpp alloc_pair); 0 (plain) for the primitives' states.
   uint64_t gm = 0;
-  // minimum items per thread of streaming (non-reducing) direct / diagonal launches (knob
-  // QDC_DIRECT_IT; 0: one item per thread).  tools/pair_probe.hip streams a far q1 pair at
-  // 5.3 / 5.55 / 5.9 TB/s with 1 / 2 / 4 items per thread in flight
-  uint32_t direct_it = 0;
-  // gates with no target at chunk bit 0..5 run on the TILE family too (far targets as row
-  // bits) instead of the direct rows.  Knob QDC_TILE_FAR, one bit per op class: bit 0 reverse
-  // (both states read and written), bit 1 one-state ops, bit 2 inject / grad.  Measured at
-  // n = 28 (profiles/r2m_micro_table_tf*.txt): reverse_q1 68-70 -> 75-77 % of 8 TB/s at every
-  // far position; one-state ops were slower tiled on 2^10 / 2^11-chunk tiles (apply 77 -> 68 %
-  // at some positions), but on 2^12-chunk tiles (tile1_wide = 2) they lift the positions the
-  // direct rows lose (apply_q1 at 20 / 24 69.9 / 69.2 -> 71.6 / 71.5 %, apply_q2 (5,20) 68.0 ->
-  // 70.8 %, profiles/r4k_micro_tune.log): bits 0 and 1 on
-  uint32_t tile_far = 3;
-  // XCD-aware block order of streaming single-gate launches (direct and tile families; knob
-  // QDC_XCD_MAP): the blocks one XCD runs own adjacent ranges.  Measured at n = 28
-  // (profiles/r2t_micro_table_xcd*.txt): injections at q1 1..6 71 -> 76 %, apply/inject at
-  // q1 7..11 and 21..23 +4..7 points, apply_q2 71.6 -> 73.4 %; q1 24 71.8 -> 69.4 %.
-  // Bits: 0 streaming launches, 1 reducing launches, 2 diagonal launches (k_diag, round 6)
-  uint32_t xcd_map = 1;
-  // two-state tile-family launches on 2^10-chunk tiles (K = 4, 32 KiB of LDS per block) instead
-  // of 2^9 (knob QDC_TILE2_WIDE): longer rows per far row bit.  Measured at n = 28
-  // (profiles/r2y_micro_table_tile2_wide*.txt): reverse_q2 +1.2..3.3 points on every pair
-  // ((26,27) 66.3 -> 69.6 %, (14,13) 69.4 -> 71.4 %), reverse_q1 and injections within +-0.5
-  // (round 4: 2^11-chunk two-state tiles, 64 KiB of LDS: reverse_q2 (26,27) 69.4 -> 72.3 %,
-  // (14,13) 71.3 -> 73.8 %, reverse_q1 75.8 -> 77.5-78 %, profiles/r4k_micro_tune.log)
-  uint32_t tile2_wide = 2;
-  // one-state tile-family launches on 2^(10 + tile1_wide)-chunk tiles (1: K = 8, 32 KiB of LDS;
-  // 2: K = 16, 64 KiB; knob QDC_TILE1_WIDE)
-  uint32_t tile1_wide = 2;
-  // single-gate ops on the LANE family (k_lane: one chunk per lane, partners across lanes;
-  // knob QDC_LANE, one bit per op class: bit 0 reverse, bit 1 streaming one-state ops and
-  // injections, bit 2 densities and gradients).  Measured at n = 28 f32 (profiles/r5/
-  // r5k_*, r5l_*): apply 72-74 -> 76-84 % of 8 TB/s at most placements; the reverse with its
-  // gradient 77.5 -> 65-67 % at far targets (the tile family's 32 KiB runs per state win for
-  // two states), densities within +-1: bit 1 only
-  uint32_t lane_ops = 2;
-  // units in flight per wave of LANE launches, per class as lane_ops (knob QDC_LANE_U="u0,u1,u2";
-  // 1, 4 or 8)
-  uint32_t lane_u[3] = {8, 1, 4};
-  // chunks per state in flight per thread and step of the diagonal reverse kernels (knob
-  // QDC_DIAG_RU: 4, 8 or 16; k_diag takes 2 or 8; 8 = a block's step moves 32 KiB of each state,
-  // as the tile family): k_diag reverse_q2_diag 71.4 -> 73.3 % (profiles/r5/r5l_*); k_diag_q
-  // 74.5 / 75.4 / 76.7 % at 4 / 8 / 16 (profiles/r6/r6l)
-  uint32_t diag_ru = 16;
-  // target blocks of the diagonal reverse's reducing launches (knob QDC_DIAG_RED, <= NBMAX):
-  // k_diag_q with 16 in flight 76.7 -> 77.3 % at 2048 -> 4096 blocks (profiles/r6/r6l)
-  uint32_t diag_red = NBMAX;
-  // diagonal reverse launches on k_diag_q (k and the matrix entries fixed per thread; knob
-  // QDC_DIAG_Q = 0: k_diag)
-  uint32_t diag_q = 1;
-  // tile-family blocks of several tiles (reducing launches) load the next tile during this
-  // tile's math (knob QDC_TILE_PF), on tiles without far row bits: reverse_q2 (0,1) / (1,2)
-  // +0.7..1.0 points; with row bits it measured 2.5-3 points slower (reverse_q1 at 12..27,
-  // reverse_q2 (5,20), (27,0); profiles/r6/r6m)
-  uint32_t tile_pf = 1;
-  // streaming LANE launches with a target beyond the wave's chunk bits on the block-wide
-  // variant (k_lane_blk; knob QDC_LANE_BLK): +1..3.5 points at 13 of 27 far placements, -1..4
-  // at 5 (profiles/r5/r5m_*, r5n_*); the far-row cells that stay near 71 % (q1 20, 24) do so
-  // under every variant and block order tried: a DRAM-mapping effect of the row distance
-  // (tools/r5/stream_probe2.hip: plain two-row streams at chunk bit 20 reach 72.6 %)
-  uint32_t lane_blk = 1;
-  // Address-map exceptions of the one-state application (f32 n = 28 sweep, every q1 position
-  // and 8 q2 pairs, LANE vs its wave variant vs the tile family, two repeats on one box:
-  // profiles/r6/r6v), keyed by the byte stride 2^b of a target (b = position + 3 in f32, + 4 in
-  // f64).  The tile family streams every far q1 at a flat 73 %; LANE beats it everywhere except
-  // at b = 23 and 27 (q1 20 / 24: 72.0 / 71.5 %), where the pair's two rows collide in the
-  // DRAM map: those run on the tile family (knob QDC_LANE_TILE_BITS, a mask of b).  The wave
-  // variant of LANE beats the block-wide one at b = 15 (q1 12: 80.7 -> 85.0 %) and 23 (q2
-  // (5,20): 72.8 -> 75.0 %) and loses 1-3 points at 9 other placements (knob
-  // QDC_LANE_NOBLK_BITS).
-  uint64_t lane_tile_bits = (1ull << 23) | (1ull << 27);
-  uint64_t lane_noblk_bits = (1ull << 15) | (1ull << 23);
+  // The context's QDC_* knobs (qdc_knobs.hpp, scope Context): read() fills them from the
+  // environment when the context is created; host only, no device involved.
+  struct Knobs {
+    uint32_t grid_cap = 1u << 20;  // streaming launches: ~one item per thread (measured best)
+    uint32_t red_cap = 2048;   // target blocks of reduction launches (<= NBMAX)
+    // the same for the single-gate reverse with its gradient (both states read and written; knob
+    // QDC_REV_RED): at 4096 instead of 2048 blocks reverse_q2 +1..2 points at 5 of 7 pairs
+    // ((26,27) 72.4 -> 74.3 %, (0,1) 75.9 -> 77.1 %), reverse_q1 +0.5..1 (profiles/r6/r6m)
+    uint32_t rev_red_cap = NBMAX;
+    // minimum items per thread of streaming (non-reducing) direct / diagonal launches (knob
+    // QDC_DIRECT_IT; 0: one item per thread).  tools/pair_probe.hip streams a far q1 pair at
+    // 5.3 / 5.55 / 5.9 TB/s with 1 / 2 / 4 items per thread in flight
+    uint32_t direct_it = 0;
+    // gates with no target at chunk bit 0..5 run on the TILE family too (far targets as row
+    // bits) instead of the direct rows.  Knob QDC_TILE_FAR, one bit per op class: bit 0 reverse
+    // (both states read and written), bit 1 one-state ops, bit 2 inject / grad.  Measured at
+    // n = 28 (profiles/r2m_micro_table_tf*.txt): reverse_q1 68-70 -> 75-77 % of 8 TB/s at every
+    // far position; one-state ops were slower tiled on 2^10 / 2^11-chunk tiles (apply 77 -> 68 %
+    // at some positions), but on 2^12-chunk tiles (tile1_wide = 2) they lift the positions the
+    // direct rows lose (apply_q1 at 20 / 24 69.9 / 69.2 -> 71.6 / 71.5 %, apply_q2 (5,20) 68.0 ->
+    // 70.8 %, profiles/r4k_micro_tune.log): bits 0 and 1 on
+    uint32_t tile_far = 3;
+    // XCD-aware block order of streaming single-gate launches (direct and tile families; knob
+    // QDC_XCD_MAP): the blocks one XCD runs own adjacent ranges.  Measured at n = 28
+    // (profiles/r2t_micro_table_xcd*.txt): injections at q1 1..6 71 -> 76 %, apply/inject at
+    // q1 7..11 and 21..23 +4..7 points, apply_q2 71.6 -> 73.4 %; q1 24 71.8 -> 69.4 %.
+    // Bits: 0 streaming launches, 1 reducing launches, 2 diagonal launches (k_diag, round 6)
+    uint32_t xcd_map = 1;
+    // two-state tile-family launches on 2^10-chunk tiles (K = 4, 32 KiB of LDS per block) instead
+    // of 2^9 (knob QDC_TILE2_WIDE): longer rows per far row bit.  Measured at n = 28
+    // (profiles/r2y_micro_table_tile2_wide*.txt): reverse_q2 +1.2..3.3 points on every pair
+    // ((26,27) 66.3 -> 69.6 %, (14,13) 69.4 -> 71.4 %), reverse_q1 and injections within +-0.5
+    // (round 4: 2^11-chunk two-state tiles, 64 KiB of LDS: reverse_q2 (26,27) 69.4 -> 72.3 %,
+    // (14,13) 71.3 -> 73.8 %, reverse_q1 75.8 -> 77.5-78 %, profiles/r4k_micro_tune.log)
+    uint32_t tile2_wide = 2;
+    // one-state tile-family launches on 2^(10 + tile1_wide)-chunk tiles (1: K = 8, 32 KiB of LDS;
+    // 2: K = 16, 64 KiB; knob QDC_TILE1_WIDE)
+    uint32_t tile1_wide = 2;
+    // single-gate ops on the LANE family (k_lane: one chunk per lane, partners across lanes;
+    // knob QDC_LANE, one bit per op class: bit 0 reverse, bit 1 streaming one-state ops and
+    // injections, bit 2 densities and gradients).  Measured at n = 28 f32 (profiles/r5/
+    // r5k_*, r5l_*): apply 72-74 -> 76-84 % of 8 TB/s at most placements; the reverse with its
+    // gradient 77.5 -> 65-67 % at far targets (the tile family's 32 KiB runs per state win for
+    // two states), densities within +-1: bit 1 only
+    uint32_t lane_ops = 2;
+    // units in flight per wave of LANE launches, per class as lane_ops (knob QDC_LANE_U="u0,u1,u2";
+    // 1, 4 or 8)
+    uint32_t lane_u[3] = {8, 1, 4};
+    // chunks per state in flight per thread and step of the diagonal reverse kernels (knob
+    // QDC_DIAG_RU: 4, 8 or 16; k_diag takes 2 or 8; 8 = a block's step moves 32 KiB of each state,
+    // as the tile family): k_diag reverse_q2_diag 71.4 -> 73.3 % (profiles/r5/r5l_*); k_diag_q
+    // 74.5 / 75.4 / 76.7 % at 4 / 8 / 16 (profiles/r6/r6l)
+    uint32_t diag_ru = 16;
+    // target blocks of the diagonal reverse's reducing launches (knob QDC_DIAG_RED, <= NBMAX):
+    // k_diag_q with 16 in flight 76.7 -> 77.3 % at 2048 -> 4096 blocks (profiles/r6/r6l)
+    uint32_t diag_red = NBMAX;
+    // diagonal reverse launches on k_diag_q (k and the matrix entries fixed per thread; knob
+    // QDC_DIAG_Q = 0: k_diag)
+    uint32_t diag_q = 1;
+    // tile-family blocks of several tiles (reducing launches) load the next tile during this
+    // tile's math (knob QDC_TILE_PF), on tiles without far row bits: reverse_q2 (0,1) / (1,2)
+    // +0.7..1.0 points; with row bits it measured 2.5-3 points slower (reverse_q1 at 12..27,
+    // reverse_q2 (5,20), (27,0); profiles/r6/r6m)
+    uint32_t tile_pf = 1;
+    // streaming LANE launches with a target beyond the wave's chunk bits on the block-wide
+    // variant (k_lane_blk; knob QDC_LANE_BLK): +1..3.5 points at 13 of 27 far placements, -1..4
+    // at 5 (profiles/r5/r5m_*, r5n_*); the far-row cells that stay near 71 % (q1 20, 24) do so
+    // under every variant and block order tried: a DRAM-mapping effect of the row distance
+    // (tools/r5/stream_probe2.hip: plain two-row streams at chunk bit 20 reach 72.6 %)
+    uint32_t lane_blk = 1;
+    // Address-map exceptions of the one-state application (f32 n = 28 sweep, every q1 position
+    // and 8 q2 pairs, LANE vs its wave variant vs the tile family, two repeats on one box:
+    // profiles/r6/r6v), keyed by the byte stride 2^b of a target (b = position + 3 in f32, + 4 in
+    // f64).  The tile family streams every far q1 at a flat 73 %; LANE beats it everywhere except
+    // at b = 23 and 27 (q1 20 / 24: 72.0 / 71.5 %), where the pair's two rows collide in the
+    // DRAM map: those run on the tile family (knob QDC_LANE_TILE_BITS, a mask of b).  The wave
+    // variant of LANE beats the block-wide one at b = 15 (q1 12: 80.7 -> 85.0 %) and 23 (q2
+    // (5,20): 72.8 -> 75.0 %) and loses 1-3 points at 9 other placements (knob
+    // QDC_LANE_NOBLK_BITS).
+    uint64_t lane_tile_bits = (1ull << 23) | (1ull << 27);
+    uint64_t lane_noblk_bits = (1ull << 15) | (1ull << 23);
+    uint32_t dyn_static_pct = 35;  // QDC_DYN: static share of the fair share, % (100: off)
+    // smallest granule (tiles per grab) of a reducing dynamic tail (QDC_DYN_GRAN, a power of two
+    // <= 32): every granule writes its own partial per reduction slot, which k_dsum pre-sums —
+    // C2's reverse passes at granule 2: ~43 000 partials per Gamma slot, ~0.35 GB per flush
+    uint32_t dyn_gran_min = 1;
+    // 1: the profiler's events are default events (Prof::flags; QDC_EVENT_FENCE)
+    int event_fence = 0;
+
+    template <class K, class F>
+    static void each(K& k, F&& f) {
+      f(Knob::DYN, k.dyn_static_pct, 0, INT_MAX);
+      f(Knob::DYN_GRAN, k.dyn_gran_min);
+      f(Knob::EVENT_FENCE, k.event_fence);
+      f(Knob::GRID_CAP, k.grid_cap);
+      f(Knob::RED_CAP, k.red_cap);
+      f(Knob::REV_RED, k.rev_red_cap);
+      f(Knob::DIRECT_IT, k.direct_it);
+      f(Knob::TILE_FAR, k.tile_far);
+      f(Knob::XCD_MAP, k.xcd_map);
+      f(Knob::TILE2_WIDE, k.tile2_wide);
+      f(Knob::TILE1_WIDE, k.tile1_wide);
+      f(Knob::LANE, k.lane_ops);
+      f(Knob::DIAG_RU, k.diag_ru);
+      f(Knob::DIAG_Q, k.diag_q);
+      f(Knob::DIAG_RED, k.diag_red);
+      f(Knob::TILE_PF, k.tile_pf);
+      f(Knob::LANE_BLK, k.lane_blk);
+      f(Knob::LANE_TILE_BITS, k.lane_tile_bits);
+      f(Knob::LANE_NOBLK_BITS, k.lane_noblk_bits);
+      f(Knob::LANE_U, k.lane_u);
+    }
+    void read() {
+      each(*this, KnobRead{});
+      const uint32_t v = dyn_gran_min;
+      dyn_gran_min = (v >= 1 && v <= 32 && (v & (v - 1)) == 0) ? v : 1u;
+      if (grid_cap < 1) grid_cap = 1;
+      if (red_cap < 1) red_cap = 1;
+      if (red_cap > NBMAX) red_cap = NBMAX;
+      rev_red_cap = std::max(1u, std::min(rev_red_cap, NBMAX));
+      diag_red = std::max(1u, std::min(diag_red, NBMAX));
+    }
+  } k;
   // reduction arena
   cx* partials = nullptr;  // [FIN_MAX][NBMAX][RED]
   cx* results = nullptr;   // [FIN_MAX][RED] scratch destination for one-shot reductions
@@ -212,11 +258,6 @@ struct Ctx {
   Prof prof;
   unsigned long long* dctr = nullptr;  // 8 dynamic-tail counters (plan_dyn)
   uint64_t dbase = 0;
-  uint32_t dyn_static_pct = 35;  // QDC_DYN: static share of the fair share, % (100: off)
-  // smallest granule (tiles per grab) of a reducing dynamic tail (QDC_DYN_GRAN, a power of two
-  // <= 32): every granule writes its own partial per reduction slot, which k_dsum pre-sums —
-  // C2's reverse passes at granule 2: ~43 000 partials per Gamma slot, ~0.35 GB per flush
-  uint32_t dyn_gran_min = 1;
   // granule partials of dynamic-tail passes: [FIN_MAX][DYN_CAP][RED], slot i beside partials'
   cx* dparts = nullptr;
   cx* dsums = nullptr;  // [FIN_MAX][DYN_CAP / BLOCK][RED]: k_dsum's chunk sums
@@ -233,42 +274,8 @@ struct Ctx {
     QDC_HIP(hipHostMalloc(&host_results, sizeof(cx) * (size_t)FIN_MAX * RED));
     QDC_HIP(hipMalloc(&dctr, sizeof(unsigned long long) * 8 * FG_DCTR_STRIDE));
     QDC_TRY(dyn_reset());
-    if (const char* e = getenv("QDC_DYN")) dyn_static_pct = (uint32_t)std::max(0, atoi(e));
-    if (const char* e = getenv("QDC_DYN_GRAN")) {
-      const int v = atoi(e);
-      dyn_gran_min = (v >= 1 && v <= 32 && (v & (v - 1)) == 0) ? (uint32_t)v : 1u;
-    }
-    if (const char* e = getenv("QDC_EVENT_FENCE"))
-      prof.flags = atoi(e) ? (unsigned)hipEventDefault : (unsigned)hipEventDisableSystemFence;
-    if (const char* e = getenv("QDC_GRID_CAP")) grid_cap = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_RED_CAP")) red_cap = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_REV_RED")) rev_red_cap = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_DIRECT_IT")) direct_it = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_TILE_FAR")) tile_far = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_XCD_MAP")) xcd_map = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_TILE2_WIDE")) tile2_wide = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_TILE1_WIDE")) tile1_wide = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_LANE")) lane_ops = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_DIAG_RU")) diag_ru = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_DIAG_Q")) diag_q = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_DIAG_RED")) diag_red = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_TILE_PF")) tile_pf = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_LANE_BLK")) lane_blk = (uint32_t)atoi(e);
-    if (const char* e = getenv("QDC_LANE_TILE_BITS")) lane_tile_bits = strtoull(e, nullptr, 0);
-    if (const char* e = getenv("QDC_LANE_NOBLK_BITS")) lane_noblk_bits = strtoull(e, nullptr, 0);
-    if (const char* e = getenv("QDC_LANE_U")) {
-      unsigned u0 = 0, u1 = 0, u2 = 0;
-      if (sscanf(e, "%u,%u,%u", &u0, &u1, &u2) == 3) {
-        lane_u[0] = u0;
-        lane_u[1] = u1;
-        lane_u[2] = u2;
-      }
-    }
-    if (grid_cap < 1) grid_cap = 1;
-    if (red_cap < 1) red_cap = 1;
-    if (red_cap > NBMAX) red_cap = NBMAX;
-    rev_red_cap = std::max(1u, std::min(rev_red_cap, NBMAX));
-    diag_red = std::max(1u, std::min(diag_red, NBMAX));
+    k.read();
+    prof.flags = k.event_fence ? (unsigned)hipEventDefault : (unsigned)hipEventDisableSystemFence;
     return nullptr;
   }
   // make this context's device current (launches and allocations of a shard go to its device)
@@ -288,7 +295,7 @@ struct Ctx {
     return nullptr;
   }
   // static shares + dynamic tail of a launch of `grid` one-wave blocks over g.ntiles tiles:
-  // every block runs dyn_static_pct % of its fair share block-contiguously (g.tpb tiles), the
+  // every block runs k.dyn_static_pct % of its fair share block-contiguously (g.tpb tiles), the
   // rest is handed out by the eight pool counters; the counters then advance by ndyn / 8
   // successful grabs + grid / 8 final empty ones each, alike, which dbase follows
   // (false: no dynamic tail for this launch, g unchanged)
@@ -296,7 +303,7 @@ struct Ctx {
   // granule partials of a reducing pass within DYN_CAP per slot.
   bool plan_dyn(fgeo& g, uint32_t grid) {
     last_ndyn = 0;
-    if (!QDC_DYN_TAIL || !dctr || dyn_static_pct >= 100 || (grid & 7u) || (g.ntiles & 7u) || g.order == 1)
+    if (!QDC_DYN_TAIL || !dctr || k.dyn_static_pct >= 100 || (grid & 7u) || (g.ntiles & 7u) || g.order == 1)
       return false;
     if (g.ngrad > 0 && !dparts) {  // first reducing dynamic pass of this context
       if (hipMalloc(&dparts, sizeof(cx) * (size_t)FIN_MAX * DYN_CAP * RED) != hipSuccess ||
@@ -304,13 +311,13 @@ struct Ctx {
         (void)hipGetLastError();
         if (dparts) (void)hipFree(dparts);
         dparts = nullptr;
-        dyn_static_pct = 100;  // no room: static shares only from now on
+        k.dyn_static_pct = 100;  // no room: static shares only from now on
         return false;
       }
     }
-    uint64_t per = g.ntiles * dyn_static_pct / 100 / grid;
+    uint64_t per = g.ntiles * k.dyn_static_pct / 100 / grid;
     uint64_t ndyn = g.ntiles - per * grid;  // a multiple of 8 (ntiles and grid are)
-    uint32_t gran = g.ngrad > 0 ? dyn_gran_min : 1u;
+    uint32_t gran = g.ngrad > 0 ? k.dyn_gran_min : 1u;
     if (g.ngrad > 0)
       while (ndyn / gran > DYN_CAP || (ndyn % (8ull * gran)) != 0) {
         if (gran >= 64) return false;
@@ -322,7 +329,7 @@ struct Ctx {
           per += add;
           if (per * grid > g.ntiles) return false;
           ndyn = g.ntiles - per * grid;
-          gran = dyn_gran_min;  // re-check from the smallest granule with the new split
+          gran = k.dyn_gran_min;  // re-check from the smallest granule with the new split
         }
       }
     if (ndyn == 0) return false;
@@ -873,25 +880,25 @@ inline Plan plan_for(const Ctx& c, uint32_t n, uint32_t pos2, uint32_t pos1, boo
   const uint32_t cls = writes_both ? 0u : two ? 2u : 1u;  // QDC_TILE_FAR bit
   Plan p;
   const uint32_t lcls = writes_both ? 0u : reduces ? 2u : 1u;  // QDC_LANE bit
-  const uint32_t rcap = writes_both ? c.rev_red_cap : c.red_cap;
-  // byte-stride bits of the targets (Ctx::lane_tile_bits / lane_noblk_bits)
+  const uint32_t rcap = writes_both ? c.k.rev_red_cap : c.k.red_cap;
+  // byte-stride bits of the targets (Ctx::Knobs lane_tile_bits / lane_noblk_bits)
   constexpr uint32_t CXB = sizeof(cx) == 8 ? 3u : 4u;
   const uint64_t tb = ((uint64_t)1 << (pos1 + CXB)) | ((uint64_t)1 << (pos2 + CXB));
   const bool apply1 = lcls == 1 && !two;  // a one-state application (not an injection)
-  const bool lane_tile = apply1 && R == 2 && (tb & c.lane_tile_bits) != 0;
-  if (!((c.lane_ops >> lcls) & 1u) || lane_tile ||
-      !plan_lane(n, R, pos2, pos1, rcap, reduces, p, c.lane_u[lcls])) {
-    p = plan_gate(n, R, pos2, pos1, two, reduces ? rcap : c.grid_cap,
-                  (c.tile_far >> cls) & 1u, c.tile2_wide, c.tile1_wide);
-    if (!p.tile && p.g.it < c.direct_it) p.g.it = c.direct_it;
-  } else if (lcls == 1 && c.lane_blk && p.lg.nf > 0 && !(apply1 && (tb & c.lane_noblk_bits))) {
+  const bool lane_tile = apply1 && R == 2 && (tb & c.k.lane_tile_bits) != 0;
+  if (!((c.k.lane_ops >> lcls) & 1u) || lane_tile ||
+      !plan_lane(n, R, pos2, pos1, rcap, reduces, p, c.k.lane_u[lcls])) {
+    p = plan_gate(n, R, pos2, pos1, two, reduces ? rcap : c.k.grid_cap,
+                  (c.k.tile_far >> cls) & 1u, c.k.tile2_wide, c.k.tile1_wide);
+    if (!p.tile && p.g.it < c.k.direct_it) p.g.it = c.k.direct_it;
+  } else if (lcls == 1 && c.k.lane_blk && p.lg.nf > 0 && !(apply1 && (tb & c.k.lane_noblk_bits))) {
     // a far target: the block-wide variant, when the state holds a 1024-chunk unit
     Plan q;
-    if (plan_lane(n, R, pos2, pos1, c.red_cap, reduces, q, 1, 10)) p = q;
+    if (plan_lane(n, R, pos2, pos1, c.k.red_cap, reduces, q, 1, 10)) p = q;
   }
   // XCD-aware order for streaming launches only by default: reductions (few long-lived blocks
   // with contiguous ranges) measured slower with it (density 85 -> 73-82 %, profiles/r2s_*)
-  p.g.xcd = p.tg.xcd = p.lg.xcd = (c.xcd_map >> (reduces ? 1 : 0)) & 1u;  // bit 0 streaming, 1 reducing
+  p.g.xcd = p.tg.xcd = p.lg.xcd = (c.k.xcd_map >> (reduces ? 1 : 0)) & 1u;  // bit 0 streaming, 1 reducing
   // except two-state tiles whose two row bits both sit at chunk bit >= 20 (q2 pairs of far
   // qubits, row strides >= 16 MiB): XCD order measured better there, reverse_q2 (26,27)
   // 74.0 -> 75.6 %, while (14,13) drops 73.3 -> 69.1 and (5,20) / (27,0) lose 3-4 points
@@ -899,7 +906,7 @@ inline Plan plan_for(const Ctx& c, uint32_t n, uint32_t pos2, uint32_t pos1, boo
   if (p.tile && two && reduces && p.tg.h == 2 && p.tg.hb0 >= 20) p.tg.xcd = 1;
   p.g.gm = c.gm;
   p.tg.gm = c.gm;
-  p.tg.pf = c.tile_pf && p.tg.h == 0;
+  p.tg.pf = c.k.tile_pf && p.tg.h == 0;
   p.lg.gm = c.gm;
   return p;
 }
@@ -916,10 +923,10 @@ inline dgeo diag_geo(const Ctx& c, uint32_t n, uint32_t pos2, uint32_t pos1, uin
   g.gm = c.gm;
   g.nchunks = nchunks_of(n);
   g.it = per_thread(g.nchunks, target);
-  if (target == c.grid_cap && g.it < c.direct_it) g.it = c.direct_it;  // streaming
+  if (target == c.k.grid_cap && g.it < c.k.direct_it) g.it = c.k.direct_it;  // streaming
   g.p2 = pos2;
   g.p1 = pos1;
-  g.xcd = (c.xcd_map >> 2) & 1u;  // QDC_XCD_MAP bit 2: diagonal launches
+  g.xcd = (c.k.xcd_map >> 2) & 1u;  // QDC_XCD_MAP bit 2: diagonal launches
   return g;
 }
 inline uint32_t diag_blocks(const dgeo& g) {
@@ -959,7 +966,7 @@ inline bool diag_q_geo(const dgeo& g, dqgeo& q, uint32_t U) {
 
 inline const char* apply_diag(Ctx& c, cx* s, const diag4& d, uint32_t pos2, uint32_t pos1,
                               uint32_t n, const char* name) {
-  const dgeo g = diag_geo(c, n, pos2, pos1, c.grid_cap);
+  const dgeo g = diag_geo(c, n, pos2, pos1, c.k.grid_cap);
   return c.launch(name, 2.0 * state_bytes(n), k_diag<DIAG_APPLY, 4>, diag_blocks(g),
                   reinterpret_cast<chunk*>(s), (chunk*)nullptr, d, d, g, (cx*)nullptr);
 }
@@ -1000,7 +1007,7 @@ inline const char* grad_dense(Ctx& c, const cx* f, const cx* b, uint32_t pos2, u
 
 inline const char* grad_diag(Ctx& c, const cx* f, const cx* b, uint32_t pos2, uint32_t pos1,
                              uint32_t n, cx* base, uint32_t dst, int accumulate) {
-  const dgeo g = diag_geo(c, n, pos2, pos1, c.red_cap);
+  const dgeo g = diag_geo(c, n, pos2, pos1, c.k.red_cap);
   const diag4 z{};
   return reduce_into(c, base, dst, accumulate, diag_blocks(g), [&](cx* out) {
     return c.launch("grad_q2_diag", 2.0 * state_bytes(n), k_diag<DIAG_GRAD, 4>, diag_blocks(g),
@@ -1032,9 +1039,9 @@ inline const char* reverse_diag(Ctx& c, cx* f, cx* b, const diag4& d, uint32_t p
   chunk* bc = reinterpret_cast<chunk*>(b);
   const diag4 dc = conj_diag(d);
   const double bytes = 4.0 * state_bytes(n);
-  if (c.diag_q) {  // k fixed per thread (k_diag_q), when the state splits into whole blocks
-    const uint32_t U = c.diag_ru >= 16 ? 16u : c.diag_ru >= 8 ? 8u : 4u;
-    dgeo g = diag_geo(c, n, pos2, pos1, grad_base ? c.diag_red : c.grid_cap);
+  if (c.k.diag_q) {  // k fixed per thread (k_diag_q), when the state splits into whole blocks
+    const uint32_t U = c.k.diag_ru >= 16 ? 16u : c.k.diag_ru >= 8 ? 8u : 4u;
+    dgeo g = diag_geo(c, n, pos2, pos1, grad_base ? c.k.diag_red : c.k.grid_cap);
     g.it = std::max(g.it, U);
     dqgeo q;
     if (diag_q_geo(g, q, U)) {
@@ -1052,17 +1059,17 @@ inline const char* reverse_diag(Ctx& c, cx* f, cx* b, const diag4& d, uint32_t p
     }
   }
   if (grad_base) {
-    const dgeo g = diag_geo(c, n, pos2, pos1, c.red_cap);
+    const dgeo g = diag_geo(c, n, pos2, pos1, c.k.red_cap);
     return reduce_into(c, grad_base, dst, 0, diag_blocks(g), [&](cx* out) {
-      if (c.diag_ru >= 8)
+      if (c.k.diag_ru >= 8)
         return c.launch("reverse_q2_diag", bytes, k_diag<DIAG_REVERSE_GRAD, 8>, diag_blocks(g),
                         fc, bc, dc, d, g, out);
       return c.launch("reverse_q2_diag", bytes, k_diag<DIAG_REVERSE_GRAD, 2>, diag_blocks(g), fc,
                       bc, dc, d, g, out);
     });
   }
-  const dgeo g = diag_geo(c, n, pos2, pos1, c.grid_cap);
-  if (c.diag_ru >= 8)
+  const dgeo g = diag_geo(c, n, pos2, pos1, c.k.grid_cap);
+  if (c.k.diag_ru >= 8)
     return c.launch("reverse_q2_diag", bytes, k_diag<DIAG_REVERSE, 8>, diag_blocks(g), fc, bc,
                     dc, d, g, (cx*)nullptr);
   return c.launch("reverse_q2_diag", bytes, k_diag<DIAG_REVERSE, 2>, diag_blocks(g), fc, bc, dc,
@@ -1086,7 +1093,7 @@ template <int OP>
 inline const char* elementwise(Ctx& c, const cx* src, cx* dst, uint32_t n, uint64_t gm = 0) {
   const uint64_t amps = (uint64_t)1 << n;
   const uint64_t nch = amps / VEC > 0 ? amps / VEC : 1;
-  const uint32_t it = per_thread(nch, c.grid_cap);
+  const uint32_t it = per_thread(nch, c.k.grid_cap);
   const uint32_t grid = (uint32_t)((nch + (uint64_t)BLOCK * it - 1) / ((uint64_t)BLOCK * it));
   const double bytes = (OP == 2 ? 3.0 : OP >= 3 ? 1.0 : 2.0) * state_bytes(n);
   static const char* names[5] = {"copy", "conj_and_double", "add", "set_standard", "zero"};
@@ -1097,7 +1104,7 @@ inline const char* elementwise(Ctx& c, const cx* src, cx* dst, uint32_t n, uint6
 template <int OP>
 inline const char* elementwise_count(Ctx& c, const cx* src, cx* dst, uint64_t count) {
   const uint64_t nch = count / VEC > 0 ? count / VEC : 1;
-  const uint32_t it = per_thread(nch, c.grid_cap);
+  const uint32_t it = per_thread(nch, c.k.grid_cap);
   const uint32_t grid = (uint32_t)((nch + (uint64_t)BLOCK * it - 1) / ((uint64_t)BLOCK * it));
   return c.launch("reduce_sum", 0.0, k_elementwise<OP>, grid, src, dst, count, it, (uint64_t)0);
 }
@@ -1113,10 +1120,7 @@ inline const char* pack(Ctx& c, const cx* src, cx* dst, const unsigned* victims,
   for (uint32_t k = 0; k < g; ++k) pg.vc[k] = victims[k] - LV;
   // LDS tiles (k_pack_tile) whenever a tile fits the shard: every victim layout moves at
   // streaming rates (QDC_PACK_TILE=0: the direct kernel)
-  static const bool tiled = [] {
-    const char* e = getenv("QDC_PACK_TILE");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool tiled = knob_int(Knob::PACK_TILE, 1) != 0;
   if (tiled && g <= 3 && pg.nchunks >= ((uint64_t)2 << PACK_KB) && pg.lowc >= PACK_KB) {
     packtile pt{};
     pt.nchunks = pg.nchunks;
@@ -1148,7 +1152,7 @@ inline const char* diag_inject(Ctx& c, const cx* f, cx* b, const diag_tab& T, ui
   const uint64_t amps = (uint64_t)1 << n;
   const uint64_t nch = amps / VEC > 0 ? amps / VEC : 1;
   if (amps < (uint64_t)VEC) return fail("internal: diagonal injection on a state below one chunk");
-  const uint32_t it = per_thread(nch, c.grid_cap);
+  const uint32_t it = per_thread(nch, c.k.grid_cap);
   const uint32_t grid = (uint32_t)((nch + (uint64_t)BLOCK * it - 1) / ((uint64_t)BLOCK * it));
   const double bytes = (acc ? 3.0 : 2.0) * state_bytes(n);
   const chunk* fc = reinterpret_cast<const chunk*>(f);

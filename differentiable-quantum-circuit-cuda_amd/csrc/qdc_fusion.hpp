@@ -11,6 +11,7 @@
 
 #include "qdc/circuit.h"
 #include "qdc_kernels.hpp"
+#include "qdc_knobs.hpp"
 #include "qdc_rq.hpp"
 #include "qdc_shard.hpp"
 
@@ -592,10 +593,7 @@ struct RqPlan {
 // map to nothing, gave 2.06).  XOR-linear, so addresses stay tp ^ rp[j]; a bijection (the high
 // bits are unchanged).  QDC_RQ_SWZ=0: swz.  f64 (16-B entries, other bank grouping): swz.
 inline bool rq_swz_on() {
-  static const bool on = [] {
-    const char* e = getenv("QDC_RQ_SWZ");
-    return !(e && atoi(e) == 0);
-  }();
+  static const bool on = knob_int(Knob::RQ_SWZ, 1) != 0;
   return on;
 }
 inline uint32_t rq_swz(uint32_t i) {

@@ -65,11 +65,8 @@ inline uint64_t spec_hash(const std::string& s) {
 // one v_xor per access on conflict-free swizzled addresses (r3q, C2 n = 28: reverse 2.569 vs
 // 2.537 ms, forward 1.278 vs 1.221 ms per launch)
 inline bool spec_imm() {
-  static const int on = [] {
-    const char* e = getenv("QDC_SPEC_IMM");
-    return e ? atoi(e) : 0;
-  }();
-  return on != 0;
+  static const bool on = knob_int(Knob::SPEC_IMM, 0) != 0;
+  return on;
 }
 // Source of one pass program: steps as emitted into the program (relayouts with the layouts
 // before and after, stages with their fop), in order.
@@ -547,8 +544,7 @@ class SpecJit {
         }
         std::vector<std::string> names, srcs;
         std::vector<size_t> todo;
-        size_t take = (size_t)jobs_now();
-        if (const char* e = getenv("QDC_JIT_ASYNC_JOBS")) take = (size_t)std::max(1, atoi(e));
+        size_t take = (size_t)knob_int(Knob::JIT_ASYNC_JOBS, jobs_now(), 1, INT_MAX);
         take = std::min(queue.size(), take);
         for (size_t k = 0; k < take; ++k) {
           names.push_back(queue.front().first);
@@ -645,7 +641,7 @@ class SpecJit {
   // QDC_JIT_DIR, else $XDG_CACHE_HOME/qdc_jit, $HOME/.cache/qdc_jit, /tmp/qdc_jit_<uid>: the
   // first that passes secure_dir
   bool choose_dir(std::string& why) {
-    if (const char* d = getenv("QDC_JIT_DIR")) {
+    if (const char* d = knob_text(Knob::JIT_DIR)) {
       dir = d;
       return secure_dir(dir, false, why);
     }
@@ -709,11 +705,11 @@ class SpecJit {
     const std::string libdir = cut == std::string::npos ? "." : lib.substr(0, cut);
     csrc = libdir + "/../csrc";
     inc = libdir + "/../../include";
-    if (const char* sd = getenv("QDC_SRC_DIR")) {  // a library built elsewhere (A/B builds)
+    if (const char* sd = knob_text(Knob::SRC_DIR)) {  // a library built elsewhere (A/B builds)
       csrc = sd;
       inc = std::string(sd) + "/../../include";
     }
-    const char* h = getenv("QDC_HIPCC");
+    const char* h = knob_text(Knob::HIPCC);
     const char* rp = getenv("ROCM_PATH");
     hipcc = h ? h : (rp ? std::string(rp) + "/bin/hipcc" : "/opt/rocm/bin/hipcc");
     if (!exists(csrc + "/qdc_spec.hpp") || access(hipcc.c_str(), X_OK) != 0) {
@@ -761,7 +757,7 @@ class SpecJit {
     }
     fp = spec_fingerprint(spec_defines(), ident, sfp);
     {
-      const char* pe = getenv("QDC_JIT_PREBUILT");
+      const char* pe = knob_text(Knob::JIT_PREBUILT);
       std::string p = pe ? std::string(pe) : libdir + "/../jit-prebuilt";
       struct stat st;
       if ((pe && std::string(pe) == "0") || p == dir || lstat(p.c_str(), &st) != 0 ||
@@ -778,8 +774,8 @@ class SpecJit {
   }
   // compile parallelism of this process: the node's hipcc processes shared by the job's ranks
   int jobs_now() const {
-    int jobs = std::min((int)std::thread::hardware_concurrency(), 16) / procs;
-    if (const char* e = getenv("QDC_JIT_JOBS")) jobs = atoi(e);
+    const int jobs =
+        knob_int(Knob::JIT_JOBS, std::min((int)std::thread::hardware_concurrency(), 16) / procs);
     return std::max(1, std::min(jobs, 16));
   }
   // The missing kernels `todo`: one process compiles each.  Work-stealing over per-kernel locks
@@ -799,8 +795,7 @@ class SpecJit {
       flock(fd, LOCK_UN);
       close(fd);
     };
-    double wait_lim = 900;
-    if (const char* e = getenv("QDC_JIT_WAIT_S")) wait_lim = atof(e);
+    const double wait_lim = knob_double(Knob::JIT_WAIT_S, 900);
     const int jobs = jobs_now();
     std::vector<size_t> rem = todo;
     // start at a process-dependent kernel: concurrent ranks begin on different locks
@@ -893,8 +888,7 @@ class SpecJit {
                const std::vector<size_t>& todo) {
     const double t0 = now();
     const int jobs = jobs_now();
-    const char* keep_env = getenv("QDC_JIT_KEEP");  // keep sources and logs of good compiles
-    const bool keep = keep_env && atoi(keep_env) != 0;
+    const bool keep = knob_int(Knob::JIT_KEEP, 0) != 0;  // keep sources and logs of good compiles
     struct Job {
       pid_t pid;
       size_t i;

@@ -348,8 +348,7 @@ inline const char* pauli_plan(const unsigned long long* xm, const unsigned long 
 
 // QDC_PAULI_GRID: a block-count override of both kernels (tests: the stride loops at a small n)
 inline uint32_t pauli_grid(uint64_t units, uint32_t cap) {
-  if (const char* eg = getenv("QDC_PAULI_GRID"))
-    cap = (uint32_t)std::min<long>(std::max<long>(1, atol(eg)), (long)cap);
+  cap = (uint32_t)knob_long(Knob::PAULI_GRID, (long)cap, 1, (long)cap);
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(units, cap));
 }
 
@@ -378,7 +377,7 @@ inline const char* pauli_energy(Ctx& c, const cx* s, const PauliPlan& P, uint32_
     for (size_t l = l0; l < l1; ++l) {
       const bool window = l < P.win.size();
       const ptab& T = window ? P.win[l] : P.far[l - P.win.size()];
-      const uint32_t grid = pauli_grid(window ? g.ntiles : g.spans, c.red_cap);
+      const uint32_t grid = pauli_grid(window ? g.ntiles : g.spans, c.k.red_cap);
       QDC_TRY(reduce_into(c, c.results, (uint32_t)(l - l0), 0, grid, [&](cx* out) {
         if (window)
           return c.launch_block("pauli_window", state_bytes(n), k_pauli_window<false, false>, grid,

@@ -413,31 +413,29 @@ inline const char* apply_qk(Ctx& c, cx* s, const qdc_complex* U, const size_t* p
   // 16-B accesses (two adjacent groups per lane) when qubit 0 is not a target (f32); measured
   // at n = 28 (tools/qk_probe.py): k = 3 +5-7 %, k = 5 +5 %, k = 4 -10 % (kept at 8 B)
   bool pair = sizeof(real) == 4 && g.sorted[0] != 0 && k != 4;
-  if (const char* ev = getenv("QDC_QK_PAIR")) {
-    const int v = atoi(ev);  // 0 off, 2: also at k = 4 (A/B)
+  {
+    const int v = knob_int(Knob::QK_PAIR, 1);  // 0 off, 2: also at k = 4 (A/B)
     pair = v == 2 ? sizeof(real) == 4 && g.sorted[0] != 0 : pair && v != 0;
   }
   // batches per wave iteration (k_qk NB): 4 / 2 / 1 at k = 3 / 4 / 5, doubled ("wide": more
   // bytes in flight per wave) at k >= 4 — measured at n = 28 (tools/qk_probe.py,
   // profiles/r2o_qk_probe.log): k = 3 neutral, k = 4 +2 %, k = 5 +7 %.  Knob QDC_QK_WIDE=0/1
-  const char* ew = getenv("QDC_QK_WIDE");
-  bool wide = ew ? atoi(ew) != 0 : k >= 4;
+  bool wide = knob_int(Knob::QK_WIDE, k >= 4) != 0;
   // software-pipelined batches (k_qk PF; knob QDC_QK_PF=0/1): NB batches in flight while the
   // previous NB run on the matrix cores — replaces "wide" (same registers).  Measured at n = 28
   // (tools/qk_probe.py --pf, profiles/r4i_qk_pf_ab.log): k = 3 0.643 -> 0.676, k = 5 0.515 ->
   // 0.562 of HBM, k = 4 0.573 -> 0.568; on by default at k = 3, 5.  With the doubled batches
   // (QDC_QK_PF=2, profiles/r4m_qk_ab.log): k = 3 0.676 -> 0.705, k = 4 0.577 -> 0.580, k = 5
   // 0.563 -> 0.549: the default at k = 3
-  const char* epf = getenv("QDC_QK_PF");
-  const int pfv = epf ? atoi(epf) : (k == 3 ? 2 : k == 5 ? 1 : 0);
+  const int pfv = knob_int(Knob::QK_PF, k == 3 ? 2 : k == 5 ? 1 : 0);
   const bool pf = pfv != 0;
   const bool pfwide = pfv == 2;  // pipelined with the doubled batches (A/B)
   if (pf) wide = false;
   const uint64_t nb = (k == 3 ? 4 : k == 4 ? 2 : 1) * ((wide || pfwide) ? 2 : 1);
   const uint64_t gpb = pair ? 32 : 16;  // groups per batch
   const uint64_t waves = ((g.ngroups + gpb - 1) / gpb + nb - 1) / nb;
-  uint32_t gmax = 256u * 16u;  // blocks (QDC_QK_GRID: another cap, A/B)
-  if (const char* eg = getenv("QDC_QK_GRID")) gmax = (uint32_t)std::max(1, atoi(eg));
+  // blocks (QDC_QK_GRID: another cap, A/B)
+  const uint32_t gmax = (uint32_t)knob_int(Knob::QK_GRID, 256 * 16, 1, INT_MAX);
   const uint32_t grid = (uint32_t)std::min<uint64_t>((waves + 3) / 4, gmax);
   c.next_flops = 8.0 * C * (double)((uint64_t)1 << n);  // C complex MACs per amplitude
   const double bytes = 2.0 * state_bytes(n);
@@ -450,8 +448,7 @@ inline const char* apply_qk(Ctx& c, cx* s, const qdc_complex* U, const size_t* p
   // through k_qk's paired groups (0.72 against 0.62), so k = 3 stages from two
   uint32_t nlow = 0;
   for (uint32_t b = 0; b < k; ++b) nlow += pos[b] < 5;
-  int lds_min = k == 3 ? 2 : 1;
-  if (const char* el = getenv("QDC_QK_LDS")) lds_min = atoi(el);
+  const int lds_min = knob_int(Knob::QK_LDS, k == 3 ? 2 : 1);
   qkl_geo lg;
   if (lds_min > 0 && (int)nlow >= lds_min && qkl_plan(pos, k, n, lg)) {
     // tiles per wave iteration: 8 KiB per wave in f32 at k >= 4
@@ -460,8 +457,7 @@ inline const char* apply_qk(Ctx& c, cx* s, const qdc_complex* U, const size_t* p
     // Same-box A/B (profiles/r4z_qkl_pf_ab.log, bench.py's placements, two repeats): k = 4
     // 0.648 / 0.640 -> 0.653 / 0.652, k = 5 0.617 / 0.612 -> 0.634 / 0.635 (2: 0.621 / 0.624),
     // k = 3 neutral
-    int var = 1;
-    if (const char* ev = getenv("QDC_QKL_VAR")) var = atoi(ev);
+    const int var = knob_int(Knob::QKL_VAR, 1);
     const bool lpf = var != 0;
     const bool half5 = var == 2 || f64;
     const uint64_t nbl = k == 3 ? (f64 ? 2 : 4) : (k == 5 && half5) ? 1 : 2;

@@ -344,9 +344,8 @@ inline const char* reduce_qk(Ctx& c, const cx* f, const cx* b, qdc_complex* out,
       QDC_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
       res = (uint32_t)std::max(1, std::min(per_cu, 4) * cus);
     }
-    uint32_t gmax = std::min(res, QKG_GRID_MAX);
-    if (const char* eg = getenv("QDC_QKG_GRID"))
-      gmax = (uint32_t)std::min<long>(std::max<long>(1, atol(eg)), (long)QKG_GRID_MAX);
+    const uint32_t gmax = (uint32_t)knob_long(Knob::QKG_GRID, (long)std::min(res, QKG_GRID_MAX), 1,
+                                              (long)QKG_GRID_MAX);
     const uint64_t waves = (g.l.ntiles + nb - 1) / nb;
     grid = (uint32_t)std::min<uint64_t>((waves + 3) / 4, gmax);
   }

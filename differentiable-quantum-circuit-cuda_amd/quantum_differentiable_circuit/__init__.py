@@ -444,6 +444,18 @@ def rq_variant(two, tile_bits, precision="f32"):
             "spec": spec, "spec_half": half, "own_grid": bool(out[3]), "keep": bool(out[4])}
 
 
+def knob_table(precision="f32"):
+    """The QDC_* environment knobs the library reads (csrc/qdc_knobs.hpp; qdc_knob_table, host
+    only): a list of (name, scope, default text, effective value, effect).  scope says when the
+    knob is read: "Process", "Context", "Circuit", "Call" or "Hook".  The effective value is what
+    a context / a circuit created under the current environment would hold, for those two scopes;
+    "" for the others."""
+    lib = load(precision)
+    buf = C.create_string_buffer(int(lib.qdc_knob_table(None, 0)))
+    lib.qdc_knob_table(buf, len(buf))
+    return [tuple(line.split("\t")) for line in buf.value.decode().splitlines()]
+
+
 def spec_selftest(tile_bits, stages, deps=None, precision="f32"):
     """Compile the specialized kernel of a pass (host only: the runtime's generator and hipcc,
     qdc_spec_selftest): f32 tile_bits 11, a five-slot two-state reverse pass; 12, a four-slot

@@ -38,6 +38,7 @@ RUNTIME = (
     "qdc_rq_plan", "qdc_spec_selftest", "qdc_gate_plan", "qdc_lane_plan", "qdc_qkgate", "qdc_qkgrad", "qdc_qkdensity", "qdc_abi_sync", "qdc_abi_profile", "qdc_abi_profile_collect",
     "qdc_jit_stats", "qdc_jit_dir", "qdc_spec_fingerprint", "qdc_spec_selftest_batch",
     "qdc_jit_wait", "qdc_precompile", "qdc_check_schedule", "qdc_trace_program", "qdc_rq_variant",
+    "qdc_knob_table",
     "qdc_pauli_energy", "qdc_pauli_inject", "qdc_pauli_plan",
 )
 
@@ -156,6 +157,7 @@ def _proto(lib):
         "qdc_spec_fingerprint": (_E, [C.c_char_p, C.c_char_p, C.c_char_p,
                                       C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
         "qdc_rq_variant": (C.c_char_p, [C.c_int, C.c_uint, C.POINTER(C.c_uint), C.c_char_p, _S]),
+        "qdc_knob_table": (_S, [C.c_char_p, _S]),
         "qdc_rq_plan": (_S, [C.c_uint, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint),
                              C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong), _S,
                              C.POINTER(C.c_uint), _S]),

@@ -231,6 +231,14 @@ size_t qdc_rq_plan(unsigned tile_bits, unsigned slots, const unsigned* kinds, co
  * error a pass on such a tile gets. */
 const char* qdc_rq_variant(int two, unsigned tile_bits, unsigned* out, char* text_out, size_t cap);
 
+/* Test hook (host only): the table of the QDC_* environment knobs (csrc/qdc_knobs.hpp), one line
+ * per knob: name, scope (Process, Context, Circuit, Call or Hook: when it is read), default,
+ * effective value and effect, separated by tabs.  The effective value is filled for Context and
+ * Circuit knobs: what a context / a circuit created under the current environment would hold
+ * (parsed and clamped; no device is touched); empty for the other scopes.  Writes at most cap
+ * bytes to out (nullable), returns the bytes the whole table needs, its final NUL included. */
+size_t qdc_knob_table(char* out, size_t cap);
+
 /* Test hook (host only): the specialized kernel of a pass over n stages (kinds / t1 / t2 / deps
  * as qdc_rq_plan) — f32 tile_bits 11: a five-slot two-state reverse pass, every stage
  * accumulating Gamma; 12: a four-slot one-state forward pass; f64: 10 two-state, 11 one-state: the
