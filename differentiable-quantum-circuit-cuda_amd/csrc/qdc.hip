@@ -468,6 +468,7 @@ QDC_API size_t qdc_fusion_schedule(size_t local_qubits, int backward, size_t fir
   P.permute = qdc::knob_int(Knob::SCHED_PERM, P.permute) != 0;  // f64: rq_grad only
   P.mirror = qdc::knob_int(Knob::SCHED_MIRROR, P.mirror) != 0;  // QDC_MIRROR's forward
   P.defer_q1 = qdc::knob_int(Knob::DEFER_Q1, P.defer_q1) != 0;
+  P.search = qdc::knob_int(Knob::FUSE_SEARCH, P.search) != 0;
   P.perm_low = qdc::knob_uint(Knob::RQ_PERM_LOW, P.perm_low);
   P.gamma_stage_cap = qdc::knob_int(Knob::RQ_GSTAGE, P.gamma_stage_cap) != 0;
   P.split_dens = qdc::knob_int(Knob::DENS_SPLIT, P.split_dens) != 0;

@@ -305,6 +305,9 @@ struct Circuit {
     // trailing one-qubit stages of a pass join their qubit's next two-qubit stage in a later pass
     // (qdc_fusion.hpp defer_trailing_q1; QDC_DEFER_Q1)
     int defer_q1 = 1;
+    // each pass's tile chosen by search instead of by scan order (qdc_fusion.hpp search_pass;
+    // QDC_FUSE_SEARCH)
+    int fuse_search = 1;
     // grid of fused passes (QDC_FUSED_BLOCKS); 0: as many blocks as are resident at once
     // (occupancy query)
     uint32_t fused_blocks = 0;
@@ -343,6 +346,7 @@ struct Circuit {
       f(Knob::DENS_SPLIT, k.dens_split);
       f(Knob::MIRROR, k.mirror);
       f(Knob::DEFER_Q1, k.defer_q1);
+      f(Knob::FUSE_SEARCH, k.fuse_search);
       f(Knob::SCHED_CACHE, k.sched_cache_on);
       f(Knob::SPEC, k.spec_mode);
       f(Knob::SPEC_MIN_QUBITS, k.spec_min_qubits);
@@ -948,6 +952,7 @@ struct Circuit {
     P.tile1_chunks = k.tile1_chunks;
     P.mirror = mirror_on() && sched_mirror;
     P.defer_q1 = k.defer_q1 != 0;
+    P.search = k.fuse_search != 0;
     P.gamma_stage_cap = k.rq_gstage != 0;
     P.split_dens = k.dens_split != 0;
     return P;

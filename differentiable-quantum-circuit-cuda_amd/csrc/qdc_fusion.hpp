@@ -99,11 +99,15 @@ struct FusionPlanner {
   // trailing one-qubit stages move to the pass of their qubit's next two-qubit gate
   // (defer_trailing_q1; QDC_DEFER_Q1)
   bool defer_q1 = true;
-  // a forward pass holds gates or densities, not both (round 6; QDC_DENS_SPLIT): a pass with
-  // densities cannot be register-resident, so a mixed pass ran its gates on the LDS kernel
-  // (C2 n = 28: one pass of 5 gate stages + 11 densities, 2.66 ms); split, the gates run
-  // register-resident and the densities join density-only passes (k_dens1)
+  // a forward pass that holds a gate takes no density after it (round 6; QDC_DENS_SPLIT): a
+  // pass with densities cannot be register-resident, so a mixed pass ran its gates on the LDS
+  // kernel (C2 n = 28: one pass of 5 gate stages + 11 densities, 2.66 ms); split, the gates run
+  // register-resident and the densities join density-only passes (k_dens1).  Only that order
+  // is split: an unmirrored forward pass that opens with densities may still take gates on
+  // other qubits after them, and then runs on the LDS kernel.
   bool split_dens = true;
+  // each pass's tile is chosen by search_pass, not by what the scan meets first (QDC_FUSE_SEARCH)
+  bool search = true;
 
   static uint32_t log2_of(uint64_t x) {
     uint32_t k = 0;
@@ -115,8 +119,9 @@ struct FusionPlanner {
   // remaps, densities and cotangent injections) a pass may take any gate none of whose
   // earlier same-qubit gates is left for a later pass.  Each pass is built greedily in
   // program order: a gate joins if it is ready and its qubits still fit the tile, otherwise
-  // its qubits are blocked for the rest of the scan.  Per qubit, gates keep program order, so
-  // the result equals the sequential one up to floating-point rounding.
+  // its qubits are blocked for the rest of the scan (scan_pass).  Per qubit, gates keep program
+  // order, so the result equals the sequential one up to floating-point rounding.  Which
+  // qubits the tile holds is chosen first (search_pass) or left to the scan's order.
 
   uint64_t chunk_bits_of(uint32_t p) const { return p >= (uint32_t)LV ? 1ull << (p - LV) : 0ull; }
   // A full tile of 2^T chunks: lc contiguous chunk bits (>= fuse_lcmin) plus h = T - lc row
@@ -329,78 +334,233 @@ struct FusionPlanner {
       const bool gstage = two && rq_grad && gamma_stage_cap;
       const uint32_t gmax = gstage ? fuse_max_ops
                             : (two && rq_grad) ? (uint32_t)FMAX_GRAD_RQ : (uint32_t)FMAX_GRAD;
+      const PassRules rules{backward, mfwd, two, gstage, gmax, T};
       std::vector<uint32_t> rem;
       for (size_t k = i; k < j; ++k) rem.push_back((uint32_t)k);
       while (!rem.empty()) {
-        uint64_t mask = 0, blocked = 0;
-        uint32_t nred = 0;
-        uint32_t ndens = 0;  // a mirrored forward's densities (its reduction slots)
-        uint32_t left = 0;  // order classes of the ops left for a later pass
-        std::vector<uint32_t> pass, rest;
-        int kind = -1;  // reverse sweep: a pass is injections only or gates only
-        for (uint32_t k : rem) {
-          const qdc_plan_op& g = plan[k];
-          const uint64_t q = (1ull << g.pos2) | (1ull << g.pos1);
-          const bool meas = is_meas(g);
-          const uint32_t cls = op_class(g, backward);
-          // (a mirrored forward: variable gates count toward the backward's Gamma cap,
-          // densities toward the forward's reduction slots)
-          const uint32_t isred = mfwd ? (is_var(ins[g.instr].kind) ? 1u : 0u)
-                                 : ((!backward && meas) || (two && is_var(ins[g.instr].kind))) ? 1u : 0u;
-          // reverse sweep: a pass is injections only or gates only; a mirrored forward's pass
-          // is gates then densities (no gate after a density: its backward splits into the
-          // injections, then the gates' mirrored stages)
-          if ((backward && kind >= 0 && (int)meas != kind) || (mfwd && kind == 1 && !meas) ||
-              (!backward && split_dens && kind == 0 && meas) ||
-              (q & blocked) ||
-              (mfwd && meas && ndens + 1 > (uint32_t)FMAX_GRAD) ||
-              (conflicts_of(cls) & left) || pass.size() >= fuse_max_ops ||
-              nred + isred > gmax || !tile_fits(mask | op_bits(g), T)) {
-            blocked |= q;
-            left |= cls;
-            rest.push_back(k);
-            continue;
-          }
-          pass.push_back(k);
-          mask |= op_bits(g);
-          nred += isred;
-          ndens += (mfwd && meas) ? 1u : 0u;
-          kind = (int)meas;
-        }
-        // Gamma-stage cap: drop gates from the end of the pass (in pass order no kept gate
-        // depends on a dropped one) until its Gamma stages fit the accumulators
-        if (gstage && nred > (uint32_t)FMAX_GRAD_RQ) {
-          bool cut = false;
-          while (pass.size() > 1 && gamma_stages(pass, plan, !mfwd) > (uint32_t)FMAX_GRAD_RQ) {
-            rest.push_back(pass.back());
-            pass.pop_back();
-            cut = true;
-          }
-          if (cut) {
-            std::sort(rest.begin(), rest.end());
-            mask = 0;
-            for (uint32_t k : pass) mask |= op_bits(plan[k]);
-          }
-        }
-        if (defer_q1 && defer_trailing_q1(pass, rest, plan, backward)) {
-          mask = 0;
-          for (uint32_t k : pass) mask |= op_bits(plan[k]);
-        }
-        if (pass.size() == 1) {
-          items.push_back(FusionItem{0, pass});
+        ScannedPass sp = search ? search_pass(plan, rem, rules)
+                                : scan_pass(plan, rem.data(), rem.size(), rules, ~0ull, false);
+        if (sp.ops.size() == 1) {
+          items.push_back(FusionItem{0, sp.ops});
         } else {
-          FusionItem it{2, pass};
-          tile_config(mask, T, it.lc, it.h, it.hb);
+          FusionItem it{2, sp.ops};
+          tile_config(sp.mask, T, it.lc, it.h, it.hb);
           bool gates_only = it.lc >= NLOW - LV;  // the low positions are tile bits
-          for (uint32_t k : pass) gates_only = gates_only && is_gate_op(plan[k]);
-          if (permute && gates_only) permute_after(it, plan, rest, j);
+          for (uint32_t k : sp.ops) gates_only = gates_only && is_gate_op(plan[k]);
+          if (permute && gates_only) permute_after(it, plan, sp.rest, j);
           items.push_back(it);
         }
-        rem.swap(rest);
+        rem.swap(sp.rest);
       }
       i = j;
     }
     return items;
+  }
+
+  // What fuse_items fixes for the passes of one segment.
+  struct PassRules {
+    bool backward, mfwd, two, gstage;
+    uint32_t gmax, T;
+  };
+  // One pass off the front of a segment: its ops in pass order, the ops left (plan order) and
+  // the chunk bits its ops touch.
+  struct ScannedPass {
+    std::vector<uint32_t> ops, rest;
+    uint64_t mask = 0;
+  };
+  // The one place a pass is built, and so the one place every rule of a pass lives: a first-fit
+  // scan in program order over rem[0..nrem) (the segment's unscheduled ops, or a window of
+  // them).  `allowed` is a set of physical positions: a gate with a qubit outside it is treated
+  // exactly like a gate that does not fit the tile.  Whatever `allowed` is, the pass is valid;
+  // with every position allowed (and per_qubit off, defer_trailing_q1) it is the pass of the
+  // scan before the search, op for op.
+  ScannedPass scan_pass(const std::vector<qdc_plan_op>& plan, const uint32_t* rem, size_t nrem,
+                        const PassRules& r, uint64_t allowed, bool per_qubit) const {
+    const bool backward = r.backward, mfwd = r.mfwd, two = r.two;
+    ScannedPass sp;
+    std::vector<uint32_t>& pass = sp.ops;
+    std::vector<uint32_t>& rest = sp.rest;
+    uint64_t mask = 0, blocked = 0;
+    uint32_t nred = 0;
+    uint32_t ndens = 0;  // a mirrored forward's densities (its reduction slots)
+    uint32_t left = 0;  // order classes of the ops left for a later pass
+    int kind = -1;  // reverse sweep: a pass is injections only or gates only
+    for (size_t x = 0; x < nrem; ++x) {
+      if ((blocked & allowed) == allowed) {  // nothing more can join: the rest is left as it is
+        rest.insert(rest.end(), rem + x, rem + nrem);
+        break;
+      }
+      const uint32_t k = rem[x];
+      const qdc_plan_op& g = plan[k];
+      const uint64_t q = (1ull << g.pos2) | (1ull << g.pos1);
+      const bool meas = is_meas(g);
+      const uint32_t cls = op_class(g, backward);
+      // (a mirrored forward: variable gates count toward the backward's Gamma cap,
+      // densities toward the forward's reduction slots)
+      const uint32_t isred = mfwd ? (is_var(ins[g.instr].kind) ? 1u : 0u)
+                             : ((!backward && meas) || (two && is_var(ins[g.instr].kind))) ? 1u : 0u;
+      // reverse sweep: a pass is injections only or gates only; a mirrored forward's pass
+      // is gates then densities (no gate after a density: its backward splits into the
+      // injections, then the gates' mirrored stages); a forward pass that holds a gate takes
+      // no density after it (split_dens)
+      if ((q & ~allowed) ||
+          (backward && kind >= 0 && (int)meas != kind) || (mfwd && kind == 1 && !meas) ||
+          (!backward && split_dens && kind == 0 && meas) ||
+          (q & blocked) ||
+          (mfwd && meas && ndens + 1 > (uint32_t)FMAX_GRAD) ||
+          (conflicts_of(cls) & left) || pass.size() >= fuse_max_ops ||
+          nred + isred > r.gmax || !tile_fits(mask | op_bits(g), r.T)) {
+        blocked |= q;
+        left |= cls;
+        rest.push_back(k);
+        continue;
+      }
+      pass.push_back(k);
+      mask |= op_bits(g);
+      nred += isred;
+      ndens += (mfwd && meas) ? 1u : 0u;
+      kind = (int)meas;
+    }
+    // Gamma-stage cap: drop gates from the end of the pass (in pass order no kept gate
+    // depends on a dropped one) until its Gamma stages fit the accumulators
+    if (r.gstage && nred > (uint32_t)FMAX_GRAD_RQ) {
+      bool cut = false;
+      while (pass.size() > 1 && gamma_stages(pass, plan, !mfwd) > (uint32_t)FMAX_GRAD_RQ) {
+        rest.push_back(pass.back());
+        pass.pop_back();
+        cut = true;
+      }
+      if (cut) std::sort(rest.begin(), rest.end());
+    }
+    if (defer_q1) defer_trailing_q1(pass, rest, plan, backward, per_qubit);
+    for (uint32_t k : pass) sp.mask |= op_bits(plan[k]);
+    return sp;
+  }
+
+  // ---- which qubits a pass holds (QDC_FUSE_SEARCH) -------------------------------------------
+  // The scan lets whatever comes first in program order claim the tile: on a layered circuit one
+  // layer's gates across the tile's width, a slab whose light cone narrows with every layer, so
+  // the pass runs dry at half the stage cap.  search_pass chooses the tile first and lets the
+  // scan fill it: a candidate is a tile (tile_positions of a set of positions), its pass is
+  // scan_pass under that tile, its score the stages of that pass.  Candidates are grown from
+  // seeds — the first ready ops of the segment: start with the seed's qubits and the low
+  // positions every tile holds; then, for each tile qubit, look at the first op left over that
+  // touches it and reaches outside the tile, and add the outside qubits (one or two positions)
+  // of the op that gains the most stages per position added (ties: program order), until the
+  // tile takes no more or the pass is at a cap.  The scan's own pass is always a candidate and
+  // wins ties, so a pass never has fewer stages than the scan's from the same frontier; and
+  // since every candidate is a scan_pass, the search cannot produce an invalid schedule.
+  // Candidates are scored on a window of the segment (SEARCH_WINDOW upcoming ops), so the
+  // search's cost per pass does not grow with the circuit; the chosen tile's pass is then
+  // scanned over the whole segment, as the scan's is.
+  // C2 n = 28 (mirrored forward, f32): 62 -> 38 gate passes at 541 -> 541 stages; C4 n = 30:
+  // 136 -> 75; 10 000 random gates at n = 33: 667 -> 504 (tests/test_fusion_search_cpu.py).
+  static constexpr size_t SEARCH_SEEDS = 8;
+  static constexpr size_t SEARCH_WINDOW = 512;
+
+  // the positions of the tile tile_config makes for a set of positions (0: none holds them)
+  uint64_t tile_positions(uint64_t pos, uint32_t T) const {
+    uint32_t lc, h, hb[64];
+    if (!tile_config(pos >> LV, T, lc, h, hb)) return 0;
+    uint64_t a = (1ull << (LV + lc)) - 1;
+    for (uint32_t r = 0; r < h; ++r) a |= 1ull << (LV + hb[r]);
+    return a;
+  }
+  static uint64_t pos_bits(const qdc_plan_op& g) { return (1ull << g.pos2) | (1ull << g.pos1); }
+
+  ScannedPass search_pass(const std::vector<qdc_plan_op>& plan, const std::vector<uint32_t>& rem,
+                          const PassRules& r) const {
+    // (the scan's pass exactly as QDC_FUSE_SEARCH=0 builds it: it wins ties, so where the search
+    // finds nothing better the pass stays the scan's, op for op)
+    ScannedPass base = scan_pass(plan, rem.data(), rem.size(), r, ~0ull, false);
+    const size_t nw = std::min(rem.size(), SEARCH_WINDOW);
+    auto stages_of = [&](const ScannedPass& p) {
+      return (uint32_t)stage_partition(p.ops, plan, r.backward).size();
+    };
+    auto at_cap = [&](const ScannedPass& p, uint32_t st) {
+      return p.ops.size() >= fuse_max_ops || (r.gstage && st >= (uint32_t)FMAX_GRAD_RQ) ||
+             p.rest.empty();
+    };
+    auto width = [&](const ScannedPass& p) {
+      uint64_t q = (1ull << NLOW) - 1;
+      for (uint32_t k : p.ops) q |= pos_bits(plan[k]);
+      return (uint32_t)__builtin_popcountll(q);
+    };
+    const uint32_t base_st = stages_of(base);
+    if (at_cap(base, base_st) || nw < 3) return base;
+
+    // candidates, by tile (each tile is scanned once per pass)
+    struct Cand {
+      uint64_t tile;
+      ScannedPass p;
+      uint32_t st;
+    };
+    std::vector<Cand> cands;
+    auto eval = [&](uint64_t tile) -> size_t {
+      for (size_t c = 0; c < cands.size(); ++c)
+        if (cands[c].tile == tile) return c;
+      Cand c{tile, scan_pass(plan, rem.data(), nw, r, tile, true), 0};
+      c.st = stages_of(c.p);
+      cands.push_back(std::move(c));
+      return cands.size() - 1;
+    };
+    uint64_t seen = 0;
+    size_t seeds = 0;
+    for (size_t x = 0; x < nw && seeds < SEARCH_SEEDS; ++x) {
+      const uint64_t sq = pos_bits(plan[rem[x]]);
+      const bool ready = !(sq & seen);
+      seen |= sq;
+      if (!ready) continue;
+      ++seeds;
+      uint64_t want = sq | ((1ull << NLOW) - 1);
+      uint64_t tile = tile_positions(want, r.T);
+      while (tile) {
+        const size_t cur = eval(tile);
+        const uint32_t cur_st = cands[cur].st;
+        if (at_cap(cands[cur].p, cur_st)) break;
+        const std::vector<uint32_t> rest = cands[cur].p.rest;  // (eval grows cands)
+        uint64_t handled = 0, best_add = 0, best_tile = 0;
+        int64_t best_gain = 0, best_cost = 0;
+        for (uint32_t k : rest) {
+          const uint64_t q = pos_bits(plan[k]);
+          const uint64_t first = q & tile & ~handled;  // tile qubits whose next op this is
+          handled |= q & tile;
+          const uint64_t add = q & ~tile;
+          if (!first || !add) continue;
+          const uint64_t t2 = tile_positions(want | q, r.T);
+          if (!t2 || t2 == tile) continue;
+          const int64_t gain = (int64_t)cands[eval(t2)].st - (int64_t)cur_st;
+          const int64_t cost = __builtin_popcountll(add);
+          if (!best_tile || gain * best_cost > best_gain * cost) {
+            best_gain = gain;
+            best_cost = cost;
+            best_add = q;
+            best_tile = t2;
+          }
+          if ((handled & tile) == tile) break;
+        }
+        if (!best_tile) break;
+        want |= best_add;
+        tile = best_tile;
+      }
+    }
+    // the best candidate: most stages, then fewest qubits, then first found; the scan's pass
+    // wins unless a candidate has more stages
+    size_t best = cands.size();
+    uint32_t best_st = base_st, best_w = 0;
+    for (size_t c = 0; c < cands.size(); ++c) {
+      if (cands[c].st <= best_st && best == cands.size()) continue;
+      const uint32_t w = width(cands[c].p);
+      if (best == cands.size() || cands[c].st > best_st || (cands[c].st == best_st && w < best_w)) {
+        best = c;
+        best_st = cands[c].st;
+        best_w = w;
+      }
+    }
+    if (best == cands.size()) return base;
+    // the chosen tile's pass over the whole segment (ops beyond the window may join)
+    ScannedPass chosen = scan_pass(plan, rem.data(), rem.size(), r, cands[best].tile, true);
+    return stages_of(chosen) > base_st ? chosen : base;
   }
 
   // A stage of one-qubit gates that ends its qubit's run in a pass, when that qubit's next op
@@ -409,8 +569,13 @@ struct FusionPlanner {
   // forward, 6 in the reverse sweep).  Only stages no later op of the pass depends on (shared
   // qubit or conflicting order classes) move; at least one stage stays.  Returns whether any
   // moved (rest stays in plan order).
+  // per_qubit (passes on a chosen qubit set): a stage of one-qubit gates on two qubits is
+  // looked at qubit by qubit.  A pass that holds one of two neighbouring qubits cuts a row of
+  // one-qubit gates, and the stage split then pairs the gates left over with the wrong
+  // neighbours: q1(b) q1(c) become a stage and q2(c, d) runs without q1(c) in it.
   bool defer_trailing_q1(std::vector<uint32_t>& pass, std::vector<uint32_t>& rest,
-                         const std::vector<qdc_plan_op>& plan, bool backward) const {
+                         const std::vector<qdc_plan_op>& plan, bool backward,
+                         bool per_qubit = false) const {
     if (pass.size() < 2 || rest.empty()) return false;
     const std::vector<std::vector<uint32_t>> sts = stage_partition(pass, plan, backward);
     if (sts.size() < 2) return false;
@@ -422,31 +587,39 @@ struct FusionPlanner {
       bool q1only = true;
       for (uint32_t k : st)
         q1only = q1only && is_gate_op(plan[k]) && plan[k].pos2 == plan[k].pos1 &&
-                 plan[k].pos2 == plan[st[0]].pos2;
+                 (per_qubit || plan[k].pos2 == plan[st[0]].pos2);
       if (!q1only) continue;
-      const uint32_t qb = plan[st[0]].pos2;
-      const uint64_t qm = 1ull << qb;
-      bool free = true;  // no later op of the pass depends on the stage
-      for (uint32_t x : st) {
-        const uint32_t cx = op_class(plan[x], backward);
-        for (uint32_t y : pass) {
-          if (y <= x || std::find(st.begin(), st.end(), y) != st.end()) continue;
-          if (std::find(moved.begin(), moved.end(), y) != moved.end()) continue;
-          const uint64_t yq = (1ull << plan[y].pos2) | (1ull << plan[y].pos1);
-          if ((yq & qm) || (conflicts_of(cx) & op_class(plan[y], backward))) free = false;
+      size_t gone = 0;
+      for (uint32_t qb : {plan[st.front()].pos2, plan[st.back()].pos2}) {
+        std::vector<uint32_t> grp;  // the stage's gates on qb: the stage itself unless per_qubit
+        for (uint32_t k : st)
+          if (plan[k].pos2 == qb && std::find(moved.begin(), moved.end(), k) == moved.end())
+            grp.push_back(k);
+        if (grp.empty()) continue;
+        const uint64_t qm = 1ull << qb;
+        bool free = true;  // no later op of the pass depends on the gates
+        for (uint32_t x : grp) {
+          const uint32_t cx = op_class(plan[x], backward);
+          for (uint32_t y : pass) {
+            if (y <= x || std::find(grp.begin(), grp.end(), y) != grp.end()) continue;
+            if (std::find(moved.begin(), moved.end(), y) != moved.end()) continue;
+            const uint64_t yq = (1ull << plan[y].pos2) | (1ull << plan[y].pos1);
+            if ((yq & qm) || (conflicts_of(cx) & op_class(plan[y], backward))) free = false;
+          }
         }
+        if (!free) continue;
+        // the qubit's next op in the rest of the window: a two-qubit gate
+        const qdc_plan_op* next = nullptr;
+        for (uint32_t k : rest)
+          if (k > grp.back() && (((1ull << plan[k].pos2) | (1ull << plan[k].pos1)) & qm)) {
+            next = &plan[k];
+            break;
+          }
+        if (!next || !is_gate_op(*next) || next->pos2 == next->pos1) continue;
+        moved.insert(moved.end(), grp.begin(), grp.end());
+        gone += grp.size();
       }
-      if (!free) continue;
-      // the qubit's next op in the rest of the window: a two-qubit gate
-      const qdc_plan_op* next = nullptr;
-      for (uint32_t k : rest)
-        if (k > st.back() && (((1ull << plan[k].pos2) | (1ull << plan[k].pos1)) & qm)) {
-          next = &plan[k];
-          break;
-        }
-      if (!next || !is_gate_op(*next) || next->pos2 == next->pos1) continue;
-      moved.insert(moved.end(), st.begin(), st.end());
-      --kept_stages;
+      if (gone == st.size()) --kept_stages;
     }
     if (moved.empty()) return false;
     std::vector<uint32_t> keep;
@@ -472,6 +645,11 @@ struct FusionPlanner {
   // Split a pass (plan indices in pass order) into stages: greedy in program order, a gate
   // joins the current stage if none of its qubits is blocked (an earlier gate on it is left
   // for a later stage) and the stage stays within two qubits.  Per qubit, order is kept.
+  // With `search`, a one-qubit gate joins a stage that so far holds one-qubit gates of one
+  // other qubit only if the next op on either qubit is the two-qubit gate on both (or there is
+  // none): passes on a chosen qubit set cut rows of one-qubit gates, and two neighbours left
+  // over (q1(b) q1(c), then q2(b, a) and q2(d, c)) would pair into a stage of their own instead
+  // of each opening its two-qubit gate's stage.
   std::vector<std::vector<uint32_t>> stage_partition(const std::vector<uint32_t>& pass,
                                                      const std::vector<qdc_plan_op>& plan,
                                                      bool backward) const {
@@ -482,7 +660,16 @@ struct FusionPlanner {
       uint64_t q = 0, blocked = 0;
       uint32_t left = 0;
       bool closed = false;
-      for (uint32_t k : rem) {
+      auto pairs_up = [&](size_t x, uint64_t both) {
+        for (size_t y = x + 1; y < rem.size(); ++y) {
+          const qdc_plan_op& n = plan[rem[y]];
+          const uint64_t nq = (1ull << n.pos2) | (1ull << n.pos1);
+          if (nq & both) return nq == both && is_gate_op(n);
+        }
+        return true;
+      };
+      for (size_t x = 0; x < rem.size(); ++x) {
+        const uint32_t k = rem[x];
         if (closed) {
           rest.push_back(k);
           continue;
@@ -501,6 +688,9 @@ struct FusionPlanner {
           bad = true;
         }
         if (!bad && __builtin_popcountll(q | gq) > 2) bad = true;
+        if (!bad && search && q && !(q & gq) && __builtin_popcountll(q) == 1 &&
+            __builtin_popcountll(gq) == 1 && !pairs_up(x, q | gq))
+          bad = true;
         if (bad) {
           blocked |= gq;
           left |= cls;

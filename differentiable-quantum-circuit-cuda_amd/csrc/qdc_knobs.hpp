@@ -100,6 +100,8 @@ enum class KnobScope { Process, Context, Circuit, Call, Hook };
     "mirrored reverse sweeps; 0: the backward schedules itself; 2: failing to mirror is an "       \
     "error")                                                                                       \
   X(DEFER_Q1, Circuit, "1", "0: trailing one-qubit stages of a pass stay there")                   \
+  X(FUSE_SEARCH, Circuit, "1",                                                                     \
+    "0: a pass's qubits are whatever the scan meets first, not chosen by search")                  \
   X(SCHED_CACHE, Circuit, "1",                                                                     \
     "0: schedule every call instead of reusing the last call's schedule")                          \
   X(SPEC, Circuit, "1",                                                                            \
