@@ -16,6 +16,7 @@
 #include "qdc_qk.hpp"
 #include "qdc_qkgrad.hpp"
 #include "qdc_pauli.hpp"
+#include "qdc_paulirot.hpp"
 
 namespace qdc {
 
@@ -396,6 +397,31 @@ __attribute__((visibility("default"))) const char* qdc_pauli_inject(
   return qdc::pauli_inject(ctx, reinterpret_cast<const qdc::cx*>(fwd),
                            reinterpret_cast<qdc::cx*>(bwd), plan, (uint32_t)n, weight,
                            accumulate != 0);
+}
+
+// ---- Pauli rotations exp(-i theta/2 P) (include/qdc/pauli.h, qdc_paulirot.hpp) ----------------
+
+__attribute__((visibility("default"))) const char* qdc_pauli_rot(
+    qdc_complex* state, unsigned long long xmask, unsigned long long zmask, double theta,
+    size_t n) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  qdc::prot T;
+  QDC_TRY(qdc::prot_make(xmask, zmask, theta, n, false, T));
+  return qdc::pauli_rot(ctx, reinterpret_cast<qdc::cx*>(state), T, (uint32_t)n);
+}
+
+__attribute__((visibility("default"))) const char* qdc_pauli_rot_reverse(
+    qdc_complex* fwd, qdc_complex* bwd, unsigned long long xmask, unsigned long long zmask,
+    double theta, size_t n, double* dtheta) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  qdc::prot T;
+  QDC_TRY(qdc::prot_make(xmask, zmask, theta, n, true, T));
+  if (fwd == bwd) return qdc::fail("fwd and bwd must be different states.");
+  if (!bwd && dtheta) return qdc::fail("A gradient needs a bwd state.");
+  return qdc::pauli_rot_reverse(ctx, reinterpret_cast<qdc::cx*>(fwd),
+                                reinterpret_cast<qdc::cx*>(bwd), T, (uint32_t)n, dtheta);
 }
 
 // host only: no context, no device

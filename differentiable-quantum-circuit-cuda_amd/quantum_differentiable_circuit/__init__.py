@@ -23,11 +23,11 @@ import numpy as np
 from .common_gates import get_cnot, get_hadamard  # noqa: E402  (common_gates.rs)
 from ._native import (PanicException, KernelStat, PlanOp, check, default_precision, load,
                       ptr, PRECISIONS)
-from .observable import PauliSum
+from .observable import PauliSum, pauli_masks
 
 __all__ = ["Circuit", "Circuit32", "Circuit64", "QuantizedTensor", "PanicException",
            "get_q1_grad", "get_q2_grad", "get_q2_grad_diag", "get_qk_grad", "data_transfer",
-           "PauliSum", "pauli_inject",
+           "PauliSum", "pauli_inject", "pauli_rot_reverse",
            "circuit_class",
            "plan", "unpermute", "get_hadamard", "get_cnot"]
 
@@ -761,6 +761,13 @@ class QuantizedTensor:
         check(self._lib.qdc_pauli_energy(self._p, *obs._args(), self.qubits_number, C.byref(e)))
         return float(e.value)
 
+    def apply_pauli_rotation(self, ops, theta):
+        """state <- exp(-i theta/2 P) state for the Pauli string ``ops`` (``"X0 Y3 Z12"`` or a
+        sequence of ``(qubit, letter)``; qdc_pauli_rot, include/qdc/pauli.h): one pass over the
+        state at any weight."""
+        x, z = pauli_masks(self.qubits_number, ops)
+        check(self._lib.qdc_pauli_rot(self._p, x, z, _real_angle(theta), self.qubits_number))
+
     def apply_q2_gate_inv(self, gate, pos2, pos1):
         g = self._gate(gate, 16)
         self._pos2(pos2, pos1)
@@ -846,3 +853,29 @@ def pauli_inject(fwd, bwd, obs: PauliSum, weight=1.0, accumulate=True):
         raise PanicException("Pauli coefficients must be real.")
     check(fwd._lib.qdc_pauli_inject(fwd._p, bwd._p, *obs._args(), fwd.qubits_number, w.real,
                                     1 if accumulate else 0))
+
+
+def _real_angle(theta) -> float:
+    """A rotation angle: a Python float, or a 0-d or 1-element array, without imaginary part."""
+    t = complex(np.asarray(theta).reshape(()))
+    if t.imag != 0.0:
+        raise PanicException("A rotation angle must be real.")
+    return t.real
+
+
+def pauli_rot_reverse(fwd, bwd, ops, theta, want_grad=True) -> float:
+    """One reverse step of ``fwd.apply_pauli_rotation(ops, theta)`` (qdc_pauli_rot_reverse), in
+    one pass over both states: fwd <- R(-theta) fwd, bwd <- R(theta)^T bwd, and dL/dtheta =
+    1/2 Im sum_i bwd[i] (P fwd)[i] (fwd, bwd as received) as the return value; 0.0 when
+    ``want_grad`` is false (a constant gate).  ``bwd=None`` (no cotangent yet) only uncomputes."""
+    x, z = pauli_masks(fwd.qubits_number, ops)
+    t = _real_angle(theta)
+    if bwd is None:
+        check(fwd._lib.qdc_pauli_rot_reverse(fwd._p, None, x, z, t, fwd.qubits_number, None))
+        return 0.0
+    if fwd.qubits_number != bwd.qubits_number:
+        raise PanicException("fwd and bwd have different lengths.")
+    d = C.c_double(0.0)
+    check(fwd._lib.qdc_pauli_rot_reverse(fwd._p, bwd._p, x, z, t, fwd.qubits_number,
+                                         C.byref(d) if want_grad else None))
+    return float(d.value)

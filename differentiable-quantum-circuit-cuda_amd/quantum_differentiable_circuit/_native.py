@@ -40,6 +40,7 @@ RUNTIME = (
     "qdc_jit_wait", "qdc_precompile", "qdc_check_schedule", "qdc_trace_program", "qdc_rq_variant",
     "qdc_knob_table",
     "qdc_pauli_energy", "qdc_pauli_inject", "qdc_pauli_plan",
+    "qdc_pauli_rot", "qdc_pauli_rot_reverse",
 )
 
 
@@ -128,6 +129,9 @@ def _proto(lib):
                                   C.POINTER(C.c_double), _S, _S, C.c_double, C.c_int]),
         "qdc_pauli_plan": (_S, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), _S, _S,
                                 C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong), _S]),
+        "qdc_pauli_rot": (_E, [_P, C.c_ulonglong, C.c_ulonglong, C.c_double, _S]),
+        "qdc_pauli_rot_reverse": (_E, [_P, _P, C.c_ulonglong, C.c_ulonglong, C.c_double, _S,
+                                       C.POINTER(C.c_double)]),
         "qdc_abi_sync": (_E, []),
         "qdc_abi_profile": (_E, [C.c_int]),
         "qdc_abi_profile_collect": (_S, [C.POINTER(KernelStat), _S]),

@@ -17,6 +17,12 @@ in place of the q1 / q2 ones:
 An observable's forward value is ``state.pauli_energy(obs)``, a Python float, at its place in
 instruction order among the densities.
 
+A Pauli rotation ``exp(-i theta/2 P)`` (``add_const_pauli_rotation`` / ``add_var_pauli_rotation``)
+takes its angle, a real scalar, from the same FIFO as the gates of its class: forward is one
+``apply_pauli_rotation``, backward one ``pauli_rot_reverse(fwd, bwd, ops, theta)`` (``bwd=None``
+before the first cotangent), and a variable rotation's gradient is dL/dtheta, a Python float at
+its place among the variable gates' gradients (0.0 before the first cotangent).
+
 Gates are 1-D arrays of 4^k values (2^k x 2^k row-major, local index bit (k-1-b) = qubit
 positions[b]); densities come back as (2^k, 2^k) arrays and gradients as 1-D arrays in forward
 order.  At k = 1, 2 every call lands on the q1 / q2 kernels, so a circuit of 1- and 2-qubit
@@ -34,11 +40,12 @@ from typing import List
 
 import numpy as np
 
-from . import (PanicException, PauliSum, QuantizedTensor, data_transfer, get_qk_grad,
-               pauli_inject)
+from . import (PanicException, PauliSum, QuantizedTensor, _real_angle, data_transfer,
+               get_qk_grad, pauli_inject, pauli_masks, pauli_rot_reverse)
 from .abi_circuit import _slice
 
-CONST_GATE, VAR_GATE, DENSITY, DIFF_DENSITY, OBSERVABLE, DIFF_OBSERVABLE = range(6)
+(CONST_GATE, VAR_GATE, DENSITY, DIFF_DENSITY, OBSERVABLE, DIFF_OBSERVABLE, CONST_ROT,
+ VAR_ROT) = range(8)
 
 
 class DenseCircuit:
@@ -80,6 +87,14 @@ class DenseCircuit:
     def get_observable_op(self, obs): self._push_observable(OBSERVABLE, obs)
     def get_observable_op_with_grad(self, obs): self._push_observable(DIFF_OBSERVABLE, obs)
 
+    def _push_rotation(self, kind, ops):
+        ops = ops if isinstance(ops, str) else tuple(ops)
+        pauli_masks(self.state.qubits_number, ops)  # its panics, when the circuit is built
+        self.instructions.append((kind, ops))
+
+    def add_const_pauli_rotation(self, ops): self._push_rotation(CONST_ROT, ops)
+    def add_var_pauli_rotation(self, ops): self._push_rotation(VAR_ROT, ops)
+
     # --- forward --------------------------------------------------------------------------
     def _forward(self, const_gates, var_gates, all_densities) -> List[np.ndarray]:
         if not self.instructions:
@@ -95,6 +110,12 @@ class DenseCircuit:
                     word = "constant" if kind == CONST_GATE else "variable"
                     raise PanicException(f"The number of {word} gates is less than required.")
                 s.apply_qk_gate(_slice(pool.popleft()), pos)
+            elif kind in (CONST_ROT, VAR_ROT):
+                pool = cg if kind == CONST_ROT else vg
+                if not pool:
+                    word = "constant" if kind == CONST_ROT else "variable"
+                    raise PanicException(f"The number of {word} gates is less than required.")
+                s.apply_pauli_rotation(pos, _real_angle(pool.popleft()))
             elif kind in (OBSERVABLE, DIFF_OBSERVABLE):
                 if kind == DIFF_OBSERVABLE or all_densities:
                     out.append(s.pauli_energy(pos))
@@ -140,6 +161,14 @@ class DenseCircuit:
                     bwd.apply_qk_gate_tr(g, pos)
                 elif kind == VAR_GATE:
                     grads.appendleft(np.zeros(1 << (2 * len(pos)), self.dtype))
+            elif kind in (CONST_ROT, VAR_ROT):
+                pool = cg if kind == CONST_ROT else vg
+                if not pool:
+                    raise PanicException("The number of gates is less than required.")
+                d = pauli_rot_reverse(fwd, bwd, pos, _real_angle(pool.pop()),
+                                      want_grad=kind == VAR_ROT)
+                if kind == VAR_ROT:
+                    grads.appendleft(d)
             elif kind == DIFF_DENSITY:
                 if not dens:
                     raise PanicException(

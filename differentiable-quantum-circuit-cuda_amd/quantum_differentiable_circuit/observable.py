@@ -53,6 +53,24 @@ def _real_coeff(c):
     return c.real
 
 
+def pauli_masks(qubits_number: int, ops):
+    """``(xmask, zmask)`` of one Pauli string on ``qubits_number`` qubits: ``ops`` is a string
+    such as ``"X0 Y3 Z12"`` (``""`` is the identity) or a sequence of ``(qubit, "X"|"Y"|"Z")``."""
+    n = int(qubits_number)
+    x = z = 0
+    for q, p in _parse_ops(ops):
+        if q < 0 or q >= n:
+            raise PanicException("pos is out of the bound.")
+        bit = 1 << q
+        if (x | z) & bit:
+            raise PanicException("a qubit appears twice in a Pauli term.")
+        if p in ("X", "Y"):
+            x |= bit
+        if p in ("Z", "Y"):
+            z |= bit
+    return x, z
+
+
 class PauliSum:
     """``PauliSum(qubits_number, [(coeff, ops), ...])``: ``ops`` is a string such as
     ``"X0 Y3 Z12"`` (``""`` is the identity) or a sequence of ``(qubit, "X"|"Y"|"Z")``.  Terms
@@ -64,18 +82,8 @@ class PauliSum:
         merged = {}
         for coeff, ops in terms:
             c = _real_coeff(coeff)
-            x = z = 0
-            for q, p in _parse_ops(ops):
-                if q < 0 or q >= n:
-                    raise PanicException("pos is out of the bound.")
-                bit = 1 << q
-                if (x | z) & bit:
-                    raise PanicException("a qubit appears twice in a Pauli term.")
-                if p in ("X", "Y"):
-                    x |= bit
-                if p in ("Z", "Y"):
-                    z |= bit
-            merged[(x, z)] = merged.get((x, z), 0.0) + c
+            key = pauli_masks(n, ops)
+            merged[key] = merged.get(key, 0.0) + c
         self._set(n, merged)
 
     @classmethod

@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""The VQE of examples/vqe_pauli.py with Pauli strings on both sides: the ansatz is made of
+Pauli rotations exp(-i theta/2 P) (DenseCircuit.add_var_pauli_rotation) and the Hamiltonian is a
+PauliSum.  Parameters go in as angles and gradients come back as floats: no gate matrices, no
+d gate / d parameter chain on the host.
+
+  python examples/qaoa_pauli.py [--qubits 20] [--layers 10] [--iters 100] [--precision f64]
+
+Per layer a ZZ rotation on every bond of the ring with theta = 2 g and an X rotation on every qubit
+with theta = 2 b: the gates exp(-i g ZZ) and exp(-i b X) vqe_pauli.py writes as matrices, so the same
+parameters give the same energy and the same gradient."""
+import argparse
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT / "differentiable-quantum-circuit-cuda_amd"))
+
+from quantum_differentiable_circuit import PauliSum  # noqa: E402
+from quantum_differentiable_circuit.dense_circuit import DenseCircuit  # noqa: E402
+
+
+def bonds(n):
+    return [(i, i + 1) for i in range(n - 1)] + ([(0, n - 1)] if n > 2 else [])
+
+
+def hamiltonian(n, field=1.0):
+    """-sum over the ring's bonds of Z_i Z_j - field sum_i X_i."""
+    return PauliSum(n, [(-1.0, f"Z{i} Z{j}") for i, j in bonds(n)]
+                    + [(-field, f"X{i}") for i in range(n)])
+
+
+def build(n, layers, precision):
+    c = DenseCircuit(n, precision)
+    c.set_state_from_vector(np.ones(1 << n, dtype=c.dtype) / np.sqrt(1 << n))
+    for _ in range(layers):
+        for i, j in bonds(n):
+            c.add_var_pauli_rotation(f"Z{i} Z{j}")
+        for i in range(n):
+            c.add_var_pauli_rotation(f"X{i}")
+    c.get_observable_op_with_grad(hamiltonian(n))
+    return c
+
+
+def angles_of(params, n):
+    """The rotations' angles in instruction order: theta = 2 g on the bonds, 2 b on the sites."""
+    nb = len(bonds(n))
+    angles = []
+    for layer in range(len(params) // 2):
+        angles += [2.0 * float(params[2 * layer])] * nb + [2.0 * float(params[2 * layer + 1])] * n
+    return angles
+
+
+def loss_and_grad(c, params, n):
+    """E = <psi|H|psi> and its gradient in the real parameters: d theta / d parameter = 2 times
+    the sum of dE/dtheta over the parameter's rotations."""
+    nb = len(bonds(n))
+    angles = angles_of(params, n)
+    (energy,) = c.forward([], angles)
+    dtheta = c.backward([1.0], [], angles)
+    grad = np.zeros(len(params))
+    k = 0
+    for layer in range(len(params) // 2):
+        grad[2 * layer] = 2.0 * sum(dtheta[k:k + nb])
+        grad[2 * layer + 1] = 2.0 * sum(dtheta[k + nb:k + nb + n])
+        k += nb + n
+    return energy, grad
+
+
+def main():
+    from scipy.optimize import minimize
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--qubits", type=int, default=20)
+    ap.add_argument("--layers", type=int, default=10)
+    ap.add_argument("--iters", type=int, default=100)
+    ap.add_argument("--precision", default="f64", choices=["f32", "f64"])
+    ap.add_argument("--seed", type=int, default=42)
+    args = ap.parse_args()
+    n = args.qubits
+    c = build(n, args.layers, args.precision)
+    params = np.random.default_rng(args.seed).normal(size=2 * args.layers)
+    calls = [0]
+
+    def loss_val_and_grad(p):
+        calls[0] += 1
+        return loss_and_grad(c, p, n)
+
+    start = time.time()
+    result = minimize(loss_val_and_grad, params, method="L-BFGS-B", jac=True,
+                      options={"maxiter": args.iters})
+    end = time.time()
+    exact_e = -2 * (1 / np.sin(np.pi / (2 * n)))
+    print(f"Exact energy: {exact_e}")
+    print(f"Found energy: {result.fun}")
+    print(f"Relative error: {abs(result.fun - exact_e) / abs(exact_e)}")
+    print(f"Number of loss value and gradient calls: {calls[0]}")
+    print(f"Time per loss value and gradient call: {(end - start) / calls[0]}")
+
+
+if __name__ == "__main__":
+    main()

@@ -48,6 +48,31 @@ size_t qdc_pauli_plan(const unsigned long long* xmask, const unsigned long long*
                       size_t terms, size_t n, unsigned* out, unsigned long long* group_x,
                       size_t cap);
 
+/* Pauli rotations (csrc/qdc_paulirot.hpp): R(theta; P) = exp(-i theta/2 P) = cos(theta/2) I -
+ * i sin(theta/2) P for the string P(xmask, zmask), one pass over the state at any weight.
+ * cos(theta/2) and sin(theta/2) are computed on the host in double and rounded once to the
+ * build's precision.  xmask = zmask = 0 is the identity string: the global phase e^{-i theta/2}.
+ * Errors: "pos is out of the bound.", "Pauli coefficients must be finite." (a non-finite
+ * theta), "fwd and bwd must be different states.". */
+
+/* state <- exp(-i theta/2 P(xmask, zmask)) state */
+const char* qdc_pauli_rot(qdc_complex* state, unsigned long long xmask,
+                          unsigned long long zmask, double theta, size_t n);
+
+/* One reverse step of that gate, in one pass over both states:
+ *   fwd <- R(-theta) fwd                      (uncompute)
+ *   *dtheta += dL/dtheta                      (skipped when dtheta == NULL: a constant gate)
+ *   bwd <- R(theta)^T bwd                     (pull-back)
+ * with dL/dtheta = Re sum_i bwd[i] (dR/dtheta fwd_in)[i] = 1/2 Im sum_i bwd[i] (P fwd_out)[i]:
+ * the gate-gradient convention of qdc_qkgrad (grad[r,c] = sum bwd[r] fwd_in[c]) chained to the
+ * real angle, fwd_out the state the call receives and fwd_in the one it leaves, bwd the
+ * cotangent at the gate's output.  The same call returns the same bits every time (one stream
+ * synchronisation when dtheta != NULL).
+ * bwd == NULL: only the uncompute (no cotangent yet); dtheta must then be NULL too. */
+const char* qdc_pauli_rot_reverse(qdc_complex* fwd, qdc_complex* bwd, unsigned long long xmask,
+                                  unsigned long long zmask, double theta, size_t n,
+                                  double* dtheta);
+
 #ifdef __cplusplus
 }
 #endif
