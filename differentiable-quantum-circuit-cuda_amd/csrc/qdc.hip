@@ -120,39 +120,41 @@ QDC_API const char* qdc_circuit_backward(qdc_circuit* c, const qdc_complex* dg, 
   return c->impl.backward(df, cf, vf, grads);
 }
 
-QDC_API const char* qdc_circuit_get_shard(qdc_circuit* c, int which, int shard,
-                                          qdc_complex* host, size_t len) {
+// state `which` of a local shard: 0 fwd, 1 initial, 2 bwd once a backward wrote it (else none)
+static const qdc::cx* state_ptr(const qdc::Shard& s, int which) {
+  return which == 0 ? s.state : which == 1 ? s.initial : s.bwd_live ? s.bwd : nullptr;
+}
+
+// amplitudes [offset, offset + len) of one local shard in physical order; whole: the shard
+// itself (qdc_circuit_get_shard: offset 0, len its size)
+static const char* read_range(qdc_circuit* c, int which, int shard, size_t offset,
+                              qdc_complex* host, size_t len, bool whole) {
   qdc::DeviceGuard keep;
   qdc::Circuit& k = c->impl;
   if (shard < 0 || (size_t)shard >= k.sh.size()) return qdc::fail("no local shard %d", shard);
-  if (len != ((size_t)1 << k.nl)) return qdc::fail("shard length mismatch");
+  const size_t size = (size_t)1 << k.nl;
+  if (whole && len != size) return qdc::fail("shard length mismatch");
+  if (offset > size || len > size - offset) return qdc::fail("range out of the shard");
   const qdc::Shard& s = k.sh[shard];
-  const qdc::cx* src = which == 0 ? s.state : which == 1 ? s.initial : s.bwd_live ? s.bwd : nullptr;
+  const qdc::cx* src = state_ptr(s, which);
   if (!src) return qdc::fail("state %d is not allocated", which);
   QDC_TRY(k.sync_all());  // every shard's work, not only this shard's stream
   QDC_TRY(s.c().use());
-  QDC_TRY(k.read_state(s, src, 0, host, len));
+  QDC_TRY(k.read_state(s, src, offset, host, len));
   QDC_HIP(hipStreamSynchronize(s.c().stream));
   return nullptr;
+}
+
+QDC_API const char* qdc_circuit_get_shard(qdc_circuit* c, int which, int shard,
+                                          qdc_complex* host, size_t len) {
+  return read_range(c, which, shard, 0, host, len, true);
 }
 
 // A range of one local shard in physical order (no qubit un-permutation): for streaming reads
 // of states too large for one host copy, e.g. the uncompute error of a 64 GiB state.
 QDC_API const char* qdc_circuit_get_range(qdc_circuit* c, int which, int shard, size_t offset,
                                           qdc_complex* host, size_t len) {
-  qdc::DeviceGuard keep;
-  qdc::Circuit& k = c->impl;
-  if (shard < 0 || (size_t)shard >= k.sh.size()) return qdc::fail("no local shard %d", shard);
-  const size_t size = (size_t)1 << k.nl;
-  if (offset > size || len > size - offset) return qdc::fail("range out of the shard");
-  const qdc::Shard& s = k.sh[shard];
-  const qdc::cx* src = which == 0 ? s.state : which == 1 ? s.initial : s.bwd_live ? s.bwd : nullptr;
-  if (!src) return qdc::fail("state %d is not allocated", which);
-  QDC_TRY(k.sync_all());
-  QDC_TRY(s.c().use());
-  QDC_TRY(k.read_state(s, src, offset, host, len));
-  QDC_HIP(hipStreamSynchronize(s.c().stream));
-  return nullptr;
+  return read_range(c, which, shard, offset, host, len, false);
 }
 
 // Unsharded circuits only (a sharded state is assembled from qdc_circuit_get_shard + layout).
@@ -205,7 +207,7 @@ QDC_API const char* qdc_circuit_gather_state(qdc_circuit* c, int which, qdc_comp
     return nullptr;
   }
   const qdc::Shard& s = k.sh[0];
-  const qdc::cx* src = which == 0 ? s.state : which == 1 ? s.initial : s.bwd_live ? s.bwd : nullptr;
+  const qdc::cx* src = state_ptr(s, which);
   // every rank takes the same path (which is the same everywhere), so none waits alone
   if (!src) return qdc::fail("state %d is not allocated", which);
   if (!s.scratch) return qdc::fail("no staging buffer");
@@ -463,7 +465,7 @@ QDC_API size_t qdc_fusion_schedule(size_t local_qubits, int backward, size_t fir
   using qdc::Knob;
   P.tile2_chunks = qdc::knob_uint(Knob::TILE2_CHUNKS, P.tile2_chunks);
   P.tile1_chunks = qdc::knob_uint(Knob::TILE1_CHUNKS, P.tile1_chunks);  // (not validated here)
-  // the runtime's f32 register-resident settings (qdc_circuit.hpp planner()): off unless asked for
+  // the runtime's f32 register-resident settings (qdc_circuit.hpp planner): off unless asked for
   P.permute = P.rq_grad = qdc::knob_int(Knob::SCHED_RQ, 0) != 0;
   P.permute = qdc::knob_int(Knob::SCHED_PERM, P.permute) != 0;  // f64: rq_grad only
   P.mirror = qdc::knob_int(Knob::SCHED_MIRROR, P.mirror) != 0;  // QDC_MIRROR's forward
@@ -478,7 +480,7 @@ QDC_API size_t qdc_fusion_schedule(size_t local_qubits, int backward, size_t fir
   for (size_t i = 0; i < items.size(); ++i) {
     const qdc::FusionItem& it = items[i];
     std::vector<std::vector<uint32_t>> stages;
-    if (it.type == 2)
+    if (it.type == qdc::ITEM_FUSED)
       stages = P.stage_partition(it.ops, pl, backward != 0);
     else
       stages.push_back(it.ops);
@@ -558,8 +560,8 @@ static const char* spec_program_for(unsigned tile_bits, const unsigned* kinds, c
   if (tile_bits == t2bits && force_one) knobs.rq_wave |= pf ? 2 | 8 : 2;
   const qdc::RqVariant* V = qdc::rq_select(two, tile_bits, knobs, false);
   if (!V || !V->prefix) return "tile_bits: not a specialized pass's tile";
-  const bool keep = spec_half && V->ns == 5;  // (emit_rq_pass's planning)
-  const qdc::RqPlan plan = qdc::rq_plan(st, tile_bits, nullptr, true, V->ns, keep);
+  const qdc::RqPlan plan =
+      qdc::rq_plan(st, tile_bits, nullptr, true, V->ns, qdc::rq_keep(*V, spec_half));
   std::vector<qdc::SpecStep> sst;
   qdc::RqLayout cur = plan.load;
   for (const qdc::RqStep& s : plan.steps) {
@@ -571,19 +573,14 @@ static const char* spec_program_for(unsigned tile_bits, const unsigned* kinds, c
       continue;
     }
     F.kind = st[s.stage].kind | (two ? qdc::FOP_GAMMA : 0u);
-    F.t1 = s.cs;
-    const uint32_t kd = st[s.stage].kind;
-    if ((kd == qdc::FK_Q2 || kd == qdc::FK_DIAG) && (s.cs >> 3) > (s.cs & 7u))
-      F.t1 = (s.cs & 7u) * 8u + (s.cs >> 3);  // the runtime's canonical S1 < S2
+    bool swapped = false;  // (no matrices here: only the case matters)
+    F.t1 = qdc::rq_slot_case(F.kind, s.cs, swapped);
     sst.push_back(qdc::SpecStep{false, cur, cur, F});
   }
-  // (spec_entry's choice: a program whose relayouts all keep a slot runs on half buffers
-  // where its variant has that form)
-  const bool half = V->pass_half && spec_half && !qdc::spec_imm() && qdc::spec_half_ok(sst);
-  const qdc::SpecKind K = qdc::spec_kind(*V, half);
-  const std::string body = qdc::spec_program_source(sst, tile_bits, K);
-  name = qdc::spec_kernel_name(body, K);
-  src = qdc::spec_kernel_source(name, body, K);
+  qdc::SpecEntry e =
+      qdc::spec_kernel_of(sst, *V, tile_bits, qdc::spec_half_buffer(*V, spec_half, sst));
+  name = std::move(e.name);
+  src = std::move(e.src);
   return nullptr;
 }
 
@@ -636,15 +633,28 @@ static const char* check_instr(int kind, unsigned p2, unsigned p1, size_t n, siz
     return qdc::fail("instruction %zu: invalid positions (%u, %u) on %zu qubits", i, p2, p1, n);
   return nullptr;
 }
-// the checked instructions of a dry circuit, as qdc_circuit_push stores them
-static const char* push_dry(qdc::Circuit& k, const int* kinds, const unsigned* pos2,
-                            const unsigned* pos1, size_t count, bool positions) {
+// a dry circuit of n qubits over `world` shards with the checked instructions, as
+// qdc_circuit_push stores them
+static const char* init_dry(qdc::Circuit& k, size_t n, int world, const int* kinds,
+                            const unsigned* pos2, const unsigned* pos1, size_t count,
+                            bool positions) {
+  QDC_TRY(k.init_dry((uint32_t)n, world));
   for (size_t i = 0; i < count; ++i) {
     QDC_TRY(check_instr(kinds[i], pos2[i], pos1[i], k.n, i, positions));
     const bool q1 = qdc::is_q1_gate(kinds[i]) || qdc::is_q1_density(kinds[i]);
     k.ins.push_back({kinds[i], pos2[i], q1 ? 0u : pos1[i]});
   }
   return nullptr;
+}
+
+// A host-only circuit's dry forward(cg, vg) then backward(dg, cg, vg) (qdc_precompile,
+// qdc_trace_program): the calls build their pass programs and stop before their first launch
+static const char* dry_forward_backward(qdc::Circuit& k, const qdc::Flat& cf, const qdc::Flat& vf,
+                                        const qdc::Flat& df) {
+  std::vector<qdc_complex> dens(std::max<size_t>(k.output_size(QDC_MODE_FORWARD), 1));
+  QDC_TRY(k.execute(QDC_MODE_FORWARD, cf, vf, dens.data()));
+  std::vector<qdc_complex> grads(std::max<size_t>(k.grad_size(), 1));
+  return k.backward(df, cf, vf, grads.data());
 }
 
 // Ahead-of-time compilation of a circuit's specialized passes (build time, no GPU): a host-only
@@ -658,13 +668,9 @@ QDC_API const char* qdc_precompile(size_t n, int world, const int* kinds, const 
                                    const size_t* dl, size_t nd, size_t* kernels) {
   if (n == 0 || n > 40 || world < 1) return qdc::fail("invalid precompile arguments");
   qdc::Circuit k;
-  QDC_TRY(k.init_dry((uint32_t)n, world));
-  QDC_TRY(push_dry(k, kinds, pos2, pos1, count, false));  // (positions: validate_forward)
+  QDC_TRY(init_dry(k, n, world, kinds, pos2, pos1, count, false));  // (positions: validate_forward)
   qdc::Flat cf(cg, cl, nc), vf(vg, vl, nv), df(dg, dl, nd);
-  std::vector<qdc_complex> dens(std::max<size_t>(k.output_size(QDC_MODE_FORWARD), 1));
-  QDC_TRY(k.execute(QDC_MODE_FORWARD, cf, vf, dens.data()));
-  std::vector<qdc_complex> grads(std::max<size_t>(k.grad_size(), 1));
-  QDC_TRY(k.backward(df, cf, vf, grads.data()));
+  QDC_TRY(dry_forward_backward(k, cf, vf, df));
   std::vector<std::string> names, srcs;
   for (const qdc::SpecEntry* e : k.dry_specs) {
     names.push_back(e->name);
@@ -700,14 +706,10 @@ QDC_API const char* qdc_trace_program(size_t n, int world, const int* kinds, con
   if (n == 0 || n > 40 || world < 1 || !n_out || (count > 0 && (!kinds || !pos2 || !pos1)))
     return qdc::fail("invalid trace arguments");
   qdc::Circuit k;
-  QDC_TRY(k.init_dry((uint32_t)n, world));
-  QDC_TRY(push_dry(k, kinds, pos2, pos1, count, true));
+  QDC_TRY(init_dry(k, n, world, kinds, pos2, pos1, count, true));
   k.tracing = true;
   qdc::Flat cf(cg, cl, nc), vf(vg, vl, nv), df(dg, dl, nd);
-  std::vector<qdc_complex> dens(std::max<size_t>(k.output_size(QDC_MODE_FORWARD), 1));
-  QDC_TRY(k.execute(QDC_MODE_FORWARD, cf, vf, dens.data()));
-  std::vector<qdc_complex> grads(std::max<size_t>(k.grad_size(), 1));
-  QDC_TRY(k.backward(df, cf, vf, grads.data()));
+  QDC_TRY(dry_forward_backward(k, cf, vf, df));
   *n_out = k.trace.size();
   for (size_t i = 0; i < k.trace.size() && i < cap; ++i)
     std::memcpy(&out[i], &k.trace[i], sizeof(qdc_trace_op));
@@ -725,12 +727,13 @@ QDC_API const char* qdc_check_schedule(size_t n, int world, const int* kinds, co
   if (n == 0 || n > 40 || world < 1 || (count > 0 && (!kinds || !pos2 || !pos1)))
     return qdc::fail("invalid schedule arguments");
   qdc::Circuit k;
-  QDC_TRY(k.init_dry((uint32_t)n, world));
-  QDC_TRY(push_dry(k, kinds, pos2, pos1, count, true));
+  QDC_TRY(init_dry(k, n, world, kinds, pos2, pos1, count, true));
   k.inexact.assign(k.ins.size(), 0);
-  std::vector<qdc_plan_op> pl = k.plan(QDC_MODE_FORWARD);
-  k.sched_mirror = true;
-  const std::vector<qdc::Circuit::Item> items = k.schedule(pl, false, SIZE_MAX);
+  qdc::Circuit::Call call(k, QDC_MODE_FORWARD, false, /*mirror=*/true);
+  call.plan = k.plan(QDC_MODE_FORWARD);
+  k.schedule(call);
+  const std::vector<qdc_plan_op>& pl = call.plan;
+  const std::vector<qdc::Circuit::Item>& items = call.items;
   qdc::QubitMap m;
   m.identity((uint32_t)n, k.g);
   size_t nsw = 0;
@@ -742,7 +745,6 @@ QDC_API const char* qdc_check_schedule(size_t n, int world, const int* kinds, co
           if (op.victims[j] == 0 || op.victims[j] >= k.nl || (j > 0 && op.victims[j] <= op.victims[j - 1]))
             return qdc::fail("remap %u: victims not local, nonzero and ascending", pi);
         }
-        m.apply(op.victims);
         continue;
       }
       const qdc::Instr& in = k.ins[op.instr];
@@ -752,7 +754,7 @@ QDC_API const char* qdc_check_schedule(size_t n, int world, const int* kinds, co
         return qdc::fail("plan op %u (instruction %d) at (%u, %u), its qubits at (%u, %u)", pi,
                          op.instr, op.pos2, op.pos1, m.phys[in.a], q1 ? m.phys[in.a] : m.phys[in.b]);
     }
-    for (const auto& sw : it.swaps) m.swap_phys(sw.first, sw.second);
+    qdc::Circuit::step_layout(m, it, pl);  // (a remap item holds its one op)
     nsw += it.swaps.size();
   }
   if (items_out) *items_out = items.size();
@@ -808,7 +810,7 @@ QDC_API const char* qdc_rq_variant(int two, unsigned tile_bits, unsigned* out, c
   const qdc::RqVariant* V = nullptr;
   QDC_TRY(k.rq_variant(two != 0, tile_bits, V));
   const unsigned v[5] = {V->threads, V->ns, V->dyn ? 1u : 0u, V->own_grid ? 1u : 0u,
-                         k.rq_keep(*V) ? 1u : 0u};
+                         qdc::rq_keep(*V, k.k.spec_half != 0) ? 1u : 0u};
   for (int i = 0; i < 5; ++i) out[i] = v[i];
   size_t w = 0;
   for (const char* s : {V->label, V->prefix ? V->pass : "", V->pass_half ? V->pass_half : ""}) {

@@ -20,7 +20,7 @@
 #include "qdc_shard.hpp"
 #include "qdc_stage.hpp"
 #include "qdc_fusion.hpp"
-#include "qdc_jit.hpp"
+#include "qdc_spec.hpp"
 
 namespace qdc {
 
@@ -56,9 +56,8 @@ inline const char* gate_mats(int kind, const qdc_complex* g, bool uncompute, Gat
 }
 
 // The assertion sequence of QuantizedTensor::apply_* (quantized_tensor.rs:100-152).
-inline const char* check_gate(const Instr& in, size_t len, uint32_t n) {
-  if (len != (size_t)gate_len(in.kind)) return fail("Incorrect len of the gate's buffer.");
-  if (is_q1_gate(in.kind)) {
+inline const char* check_density_pos(const Instr& in, uint32_t n) {
+  if (is_q1_gate(in.kind) || is_q1_density(in.kind)) {
     if (in.a >= n) return fail("pos is out of the bound.");
   } else {
     if (in.a == in.b) return fail("pos1 and pos2 must be different.");
@@ -67,15 +66,9 @@ inline const char* check_gate(const Instr& in, size_t len, uint32_t n) {
   }
   return nullptr;
 }
-inline const char* check_density_pos(const Instr& in, uint32_t n) {
-  if (is_q1_density(in.kind)) {
-    if (in.a >= n) return fail("pos is out of the bound.");
-  } else {
-    if (in.a == in.b) return fail("pos1 and pos2 must be different.");
-    if (in.b >= n) return fail("pos1 is out of the bound.");
-    if (in.a >= n) return fail("pos2 is out of the bound.");
-  }
-  return nullptr;
+inline const char* check_gate(const Instr& in, size_t len, uint32_t n) {
+  if (len != (size_t)gate_len(in.kind)) return fail("Incorrect len of the gate's buffer.");
+  return check_density_pos(in, n);
 }
 
 #define QDC_NCCL(call)                                                                   \
@@ -145,30 +138,14 @@ struct Exchange {
         if (s != d) QDC_HIP(hipStreamWaitEvent(sh[d].c().stream, ev[s], 0));
     return nullptr;
   }
-  void prof_begin(Shard& s, hipEvent_t& a, hipEvent_t& b) {
-    Ctx& c = s.c();
-    a = b = nullptr;
-    if (c.prof.on) {
-      a = c.prof.get();
-      b = c.prof.get();
-      if (a) (void)hipEventRecord(a, c.stream);
-    }
-  }
-  void prof_end(Shard& s, hipEvent_t a, hipEvent_t b, double bytes) {
-    Ctx& c = s.c();
-    if (c.prof.on && a && b) {
-      (void)hipEventRecord(b, c.stream);
-      c.prof.recs.push_back({"alltoall", bytes, 0.0, a, b});  // link bytes, not HBM bytes
-    }
-  }
 
   // Block j of send[s] (chunk amplitudes) goes to shard j and lands as block s of recv[j].
   const char* alltoall(std::vector<Shard>& sh, std::vector<cx*>& send, std::vector<cx*>& recv,
                        size_t chunk) {
     if (world == 1) return nullptr;
     const double bytes = (double)chunk * sizeof(cx) * (world - 1);  // per shard
-    std::vector<hipEvent_t> pa(sh.size()), pb(sh.size());
-    for (size_t s = 0; s < sh.size(); ++s) prof_begin(sh[s], pa[s], pb[s]);
+    std::vector<ProfSpan> span(sh.size());
+    for (size_t s = 0; s < sh.size(); ++s) span[s] = sh[s].c().prof_begin();
     if (comm) {
       QDC_NCCL(ncclAllToAll(send[0], recv[0], chunk * 2, type(), comm, sh[0].c().stream));
     } else if (!comms.empty()) {
@@ -184,7 +161,8 @@ struct Exchange {
                                  chunk * sizeof(cx), hipMemcpyDeviceToDevice, sh[d].c().stream));
       if (multi_stream) QDC_TRY(join(sh));  // no source is rewritten before every copy is done
     }
-    for (size_t s = 0; s < sh.size(); ++s) prof_end(sh[s], pa[s], pb[s], bytes);
+    for (size_t s = 0; s < sh.size(); ++s)
+      sh[s].c().prof_end(span[s], "alltoall", bytes, 0.0);  // link bytes, not HBM bytes
     return nullptr;
   }
   // in-place sum over all shards of `count` complex values (every shard's buffer holds the sum)
@@ -294,7 +272,7 @@ struct Circuit {
     // the O(1)-memory uncompute then drifts like the reference's gate-by-gate U, U^dagger sequence
     // instead of accumulating the rounding of independently formed stage products.  Sharded
     // circuits too (round 5): the forward's remap plan keeps both directions' order relations and
-    // the backward undoes its remaps in reverse (unremap).  The backward must follow a forward call
+    // the backward undoes its remaps in reverse (remap, inverse).  The backward must follow a forward call
     // with the same gates (else the backward schedules itself as usual).  On by default (round
     // 4: C5 n = 14 f32 uncompute 4.85x -> 1.4x the reference's floor; C2 n = 28 f32 ~3.5 %
     // slower, DESIGN.md "Uncompute drift").
@@ -392,9 +370,6 @@ struct Circuit {
                   two ? "two-state" : "one-state");
     return nullptr;
   }
-  // its five-slot passes (2^11 tiles) are planned to keep a slot in place across every relayout
-  // where they can, for the half-buffer specialized form (rq_plan keep)
-  bool rq_keep(const RqVariant& V) const { return k.spec_half && V.ns == 5; }
 
   // host-only dry run (init_dry): calls stop before their first launch; build_program writes
   // the pass program into dry_prog and collects the specialized kernels into dry_specs
@@ -411,13 +386,9 @@ struct Circuit {
   };
   bool tracing = false;
   std::vector<TraceOp> trace;
-  size_t trace_from = 0;
   std::vector<uint8_t> inexact;  // per instruction: gate not unitary to working precision
   std::vector<std::pair<const void*, uint32_t>> fused_resident_cache;
-  uint32_t last_fused_grid = 0;
-  uint32_t last_fused_ndyn = 0;  // granule partials per slot of the last fused launch
   unsigned char* prog_host = nullptr;  // pinned staging of the pass program (every device's copy)
-  std::vector<StagePost> stage_post;   // gradient recipes of the last backward's stages
   size_t prog_cap = 0;
 
   Ctx& ctx0() { return devs[0]->ctx; }
@@ -664,11 +635,6 @@ struct Circuit {
         widths.push_back(is_q1_density(ins[k].kind) ? 4 : 16);
       }
   }
-  size_t n_var() const {
-    size_t c = 0;
-    for (auto& in : ins) c += is_var(in.kind);
-    return c;
-  }
   size_t grad_size() const {
     size_t c = 0;
     for (auto& in : ins)
@@ -743,14 +709,18 @@ struct Circuit {
   }
 
   // --- remap: one all-to-all per state (see qdc_shard.hpp) --------------------------------
-  const char* remap(const qdc_plan_op& r, bool with_bwd) {
+  // remap(r), or (inverse) its undoing: the all-to-all first (its block exchange, block j of
+  // shard s <-> block s of shard j, is its own inverse), then the pack's inverse permutation.  A
+  // mirrored reverse sweep undoes the forward's remaps in reverse order, so each of its passes
+  // finds the physical layout its forward pass ran in.  (The layout follows in step_layout.)
+  const char* remap(const qdc_plan_op& r, bool inverse, bool with_bwd) {
     const uint32_t low = nl - g;              // amplitude bits of one all-to-all block
     const size_t chunk = (size_t)1 << low;    // amplitudes per block
     for (int which = 0; which < (with_bwd ? 2 : 1); ++which) {
       std::vector<cx*> send(sh.size()), recv(sh.size());
       for (size_t s = 0; s < sh.size(); ++s) {
         cx*& buf = which == 0 ? sh[s].state : sh[s].bwd;
-        if (r.pack) {
+        if (r.pack && !inverse) {
           QDC_TRY(sh[s].c().use());
           QDC_TRY(pack(sh[s].c(), buf, sh[s].scratch, r.victims, g, nl));
           send[s] = sh[s].scratch;
@@ -761,38 +731,16 @@ struct Circuit {
         }
       }
       QDC_TRY(ex.alltoall(sh, send, recv, chunk));
-      if (!r.pack)
-        for (size_t s = 0; s < sh.size(); ++s)
-          std::swap(which == 0 ? sh[s].state : sh[s].bwd, sh[s].scratch);
-    }
-    layout.apply(r.victims);
-    return nullptr;
-  }
-  // The inverse of remap(r): the all-to-all first (its block exchange, block j of shard s <->
-  // block s of shard j, is its own inverse), then the pack's inverse permutation.  A mirrored
-  // reverse sweep undoes the forward's remaps in reverse order, so each of its passes finds the
-  // physical layout its forward pass ran in.
-  const char* unremap(const qdc_plan_op& r, bool with_bwd) {
-    const uint32_t low = nl - g;
-    const size_t chunk = (size_t)1 << low;
-    for (int which = 0; which < (with_bwd ? 2 : 1); ++which) {
-      std::vector<cx*> send(sh.size()), recv(sh.size());
-      for (size_t s = 0; s < sh.size(); ++s) {
-        send[s] = which == 0 ? sh[s].state : sh[s].bwd;
-        recv[s] = sh[s].scratch;
-      }
-      QDC_TRY(ex.alltoall(sh, send, recv, chunk));
       for (size_t s = 0; s < sh.size(); ++s) {
         cx*& buf = which == 0 ? sh[s].state : sh[s].bwd;
-        if (r.pack) {
+        if (!r.pack) {
+          std::swap(buf, sh[s].scratch);
+        } else if (inverse) {
           QDC_TRY(sh[s].c().use());
           QDC_TRY(pack(sh[s].c(), sh[s].scratch, buf, r.victims, g, nl, true));
-        } else {
-          std::swap(buf, sh[s].scratch);
         }
       }
     }
-    layout.unapply(r.victims);
     return nullptr;
   }
 
@@ -821,7 +769,7 @@ struct Circuit {
     std::vector<uint32_t> grad_slots;  // reduction slot of each reduction op, in op order
     bool rq = false;   // register-resident pass (qdc_rq.hpp): ops include relayouts
     const RqVariant* var = nullptr;  // rq: the kernel variant that runs it (qdc_variant.hpp)
-    bool inv = false;  // a remap (type 1) run backwards: a mirrored backward undoing the forward's remap
+    bool inv = false;  // an ITEM_REMAP run backwards: a mirrored backward undoing the forward's remap
     bool dens1 = false;  // a read-only pass of one-qubit densities only: k_dens1
     uint32_t l0 = 0;   // rq: matrix-area offset (cx) of the L0 layout descriptor
     uint32_t tbits = 0;  // amplitude bits of the tile
@@ -854,18 +802,68 @@ struct Circuit {
     }
     bool same_gates(const Flat& cg, const Flat& vg) const { return same(cg, cgates) && same(vg, vgates); }
   } mrec;
-  std::vector<std::vector<SMat>>* rec_mats = nullptr;  // gate_stage records stage matrices here
+  // One execute() / backward() call: its arguments and everything the call's steps hand each
+  // other — validation's indices, the planner, the schedule, the program's layout, the sweep's
+  // progress.  Built at the top of the call; the steps below take it instead of member state.
+  struct Call {
+    const bool backward;
+    const int mode;  // QDC_MODE_RUN / QDC_MODE_FORWARD; a backward: QDC_PLAN_BACKWARD
+    // the schedule is a mirrored forward's (forward calls only: a run call has no backward to
+    // mirror and keeps the one-state schedule; a backward's own schedule never depends on it)
+    const bool mirror_fwd;
+    const FusionPlanner P;  // the call's planner (Circuit::planner)
+    const Flat *cg, *vg, *dg;  // the gates; backward: the cotangents (a schedule-only call: none)
+    std::vector<size_t> gidx;                 // per instruction: index into cg / vg / dg
+    std::vector<uint32_t> var_idx, out_idx;   // ... gradient row (backward), density slot (forward)
+    uint32_t nvar = 0;
+    std::vector<qdc_plan_op> plan;
+    std::vector<Item> items;
+    size_t first_inject = SIZE_MAX;  // backward: plan index of the first cotangent injection
+    size_t mats_off = 0;             // byte offset of the program's matrix area
+    bool have_bwd = false;           // backward: bwd holds a cotangent by now
+    // a mirrored forward records each gate stage's matrix for its backward (MirrorRec)
+    bool record = false;
+    std::vector<std::vector<SMat>> stage_mats;
+    std::vector<StagePost> stage_post;  // gradient recipes of the backward's Gamma stages
+    size_t trace_start = 0;             // the call's first entry of `trace`
+    hclock::time_point ht[6];           // host_record's stamps
+    Call(const Circuit& c, int mode_, bool backward_, bool mirror, const Flat* cg_ = nullptr,
+         const Flat* vg_ = nullptr, const Flat* dg_ = nullptr)
+        : backward(backward_), mode(mode_), mirror_fwd(mirror && !backward_), P(c.planner(mirror_fwd)),
+          cg(cg_), vg(vg_), dg(dg_), trace_start(c.trace.size()) {
+      ht[0] = hclock::now();
+    }
+    const qdc_complex* gate(const Instr& in, size_t instr) const {
+      return (is_const(in.kind) ? cg : vg)->at(gidx[instr]);
+    }
+    // the pass runs on both states (a backward's passes from its first injection on)
+    bool two_state(const Item& it) const { return backward && it.ops[0] >= first_inject; }
+  };
+  // How an item changes a qubit layout: a remap applied or undone, then the swaps of a permuting
+  // pass (it stored its tile's qubits at new positions; later ops were planned so).  The one
+  // statement of it: the sweeps (live and dry), trace_logical and qdc_check_schedule use it.
+  static void step_layout(QubitMap& m, const Item& it, const std::vector<qdc_plan_op>& pl) {
+    if (it.type == ITEM_REMAP) {
+      if (it.inv)
+        m.unapply(pl[it.ops[0]].victims);
+      else
+        m.apply(pl[it.ops[0]].victims);
+    }
+    for (const auto& sw : it.swaps) m.swap_phys(sw.first, sw.second);
+  }
   // The backward schedule as the forward's passes run in reverse (mirror mode): op positions
   // mapped into the layout each reverse pass starts from (the forward pass's store layout),
   // stages and the ops in them reversed, the forward's swaps undone in reverse order.
-  bool mirror_schedule(std::vector<qdc_plan_op>& pl, std::vector<Item>& items,
-                       size_t& first_inject) const {
+  bool mirror_schedule(Call& c) const {
+    std::vector<qdc_plan_op>& pl = c.plan;
+    std::vector<Item>& items = c.items;
+    auto is_meas = [&](const qdc_plan_op& op) { return c.P.is_meas(op); };
     pl.clear();
     items.clear();
     const std::vector<Item>& F = mrec.items;
     for (size_t k = F.size(); k-- > 0;) {
       const Item& f = F[k];
-      if (f.type != 0 && f.type != 1 && f.type != 2) return false;
+      if (f.type != ITEM_OP && f.type != ITEM_REMAP && f.type != ITEM_FUSED) return false;
       auto push = [&](uint32_t fi) {
         qdc_plan_op op = mrec.plan[fi];
         if (op.type == QDC_PLAN_OP) {
@@ -877,16 +875,16 @@ struct Circuit {
       };
       auto shell = [&]() {
         Item b;
-        b.type = 2;
+        b.type = ITEM_FUSED;
         b.lc = f.lc;
         b.h = f.h;
         for (uint32_t r = 0; r < (uint32_t)FMAX_ROWS; ++r) b.hb[r] = f.hb[r];
         return b;
       };
-      if (f.type != 2) {  // a single op, or a remap undone (unremap)
+      if (f.type != ITEM_FUSED) {  // a single op, or a remap undone
         Item b;
         b.type = f.type;
-        b.inv = f.type == 1;
+        b.inv = f.type == ITEM_REMAP;
         b.ops.push_back(push(f.ops[0]));
         items.push_back(std::move(b));
         continue;
@@ -907,7 +905,7 @@ struct Circuit {
           m.stages.push_back({bi});
         }
         if (m.ops.size() == 1) {
-          m.type = 0;
+          m.type = ITEM_OP;
           m.stages.clear();
         }
         items.push_back(std::move(m));
@@ -928,7 +926,7 @@ struct Circuit {
       }
       items.push_back(std::move(b));
     }
-    first_inject = first_injection(pl);
+    c.first_inject = first_injection(pl);
     return true;
   }
   // plan index of the first cotangent injection (the ops before it only uncompute fwd), or the
@@ -940,7 +938,7 @@ struct Circuit {
   }
   static constexpr uint32_t TILE_CHUNKS_1 = FusionPlanner::TILE_CHUNKS_1;
   static constexpr uint32_t TILE_CHUNKS_2 = FusionPlanner::TILE_CHUNKS_2;
-  FusionPlanner planner() const {
+  FusionPlanner planner(bool mirror_fwd) const {
     FusionPlanner P{ins, inexact, nl, k.fuse != 0, k.fuse_meas != 0, k.fuse_max_ops, k.fuse_lcmin};
     // gate-only passes permute their tile on the way out when they are register-resident
     // (sharded circuits too, round 5: later remaps' victims are relabelled, qdc_fusion.hpp
@@ -950,24 +948,21 @@ struct Circuit {
     P.rq_grad = k.rq_grad32 && k.use_rq && (sizeof(real) == 4 || k.rq64);
     if (k.rq_perm_low) P.perm_low = k.rq_perm_low;
     P.tile1_chunks = k.tile1_chunks;
-    P.mirror = mirror_on() && sched_mirror;
+    P.mirror = mirror_on() && mirror_fwd;
     P.defer_q1 = k.defer_q1 != 0;
     P.search = k.fuse_search != 0;
     P.gamma_stage_cap = k.rq_gstage != 0;
     P.split_dens = k.dens_split != 0;
     return P;
   }
-  bool is_meas(const qdc_plan_op& op) const { return planner().is_meas(op); }
-  std::vector<Item> fuse_items(std::vector<qdc_plan_op>& plan, bool backward,
-                               size_t first_inject = SIZE_MAX) const {
-    std::vector<Item> items;
-    for (FusionItem& f : planner().fuse_items(plan, backward, first_inject)) {
+  void fuse_items(Call& c) const {
+    c.items.clear();
+    for (FusionItem& f : c.P.fuse_items(c.plan, c.backward, c.first_inject)) {
       Item it;
       static_cast<FusionItem&>(it) = std::move(f);
-      if (it.type == 2) it.stages = planner().stage_partition(it.ops, plan, backward);
-      items.push_back(std::move(it));
+      if (it.type == ITEM_FUSED) it.stages = c.P.stage_partition(it.ops, c.plan, c.backward);
+      c.items.push_back(std::move(it));
     }
-    return items;
   }
   // The pass schedule of a call (fuse_items + stage_partition, ~1-2 ms at C2 n = 28) depends on
   // the plan, the inexact flags and the mode only, not on the gate values: the last schedule
@@ -981,9 +976,6 @@ struct Circuit {
     std::vector<Item> items;
   };
   SchedCache sched_cache[2];  // forward / run, backward
-  // the schedule being built is a mirrored forward's (forward calls only: a run call has no
-  // backward to mirror and keeps the one-state schedule)
-  bool sched_mirror = false;
   static bool same_plan(const std::vector<qdc_plan_op>& a, const std::vector<qdc_plan_op>& b) {
     if (a.size() != b.size()) return false;
     for (size_t i = 0; i < a.size(); ++i) {
@@ -996,25 +988,26 @@ struct Circuit {
     }
     return true;
   }
-  std::vector<Item> schedule(std::vector<qdc_plan_op>& plan, bool backward, size_t first_inject) {
-    SchedCache& c = sched_cache[backward ? 1 : 0];
-    if (k.sched_cache_on && c.valid && c.first_inject == first_inject && c.inexact == inexact &&
-        c.mirror == sched_mirror && same_plan(c.in_plan, plan)) {
-      plan = c.out_plan;
-      return c.items;
+  // c.plan (rewritten by the permuting passes) and c.first_inject into c.items
+  void schedule(Call& c) {
+    SchedCache& sc = sched_cache[c.backward ? 1 : 0];
+    if (k.sched_cache_on && sc.valid && sc.first_inject == c.first_inject && sc.inexact == inexact &&
+        sc.mirror == c.mirror_fwd && same_plan(sc.in_plan, c.plan)) {
+      c.plan = sc.out_plan;
+      c.items = sc.items;
+      return;
     }
-    c.valid = false;
-    c.in_plan = plan;
-    std::vector<Item> items = fuse_items(plan, backward, first_inject);
+    sc.valid = false;
+    sc.in_plan = c.plan;
+    fuse_items(c);
     if (k.sched_cache_on) {
-      c.out_plan = plan;
-      c.items = items;
-      c.inexact = inexact;
-      c.first_inject = first_inject;
-      c.mirror = sched_mirror;
-      c.valid = true;
+      sc.out_plan = c.plan;
+      sc.items = c.items;
+      sc.inexact = inexact;
+      sc.first_inject = c.first_inject;
+      sc.mirror = c.mirror_fwd;
+      sc.valid = true;
     }
-    return items;
   }
   // register-layout plans of passes (rq_plan, ~20 us each), by the pass's stages and tile
   std::map<std::vector<uint64_t>, RqPlan> rq_plan_cache;
@@ -1076,17 +1069,11 @@ struct Circuit {
     uint32_t cls;
     int slot;
   };
-  // One build_program call: its inputs, the write cursors of the program (fo fops and mo matrix
-  // values so far, the next Gamma slot) and the per-pass scratch, reserved once and reused
+  // One build_program call: the call it builds for, the write cursors of the program (fo fops
+  // and mo matrix values so far, the next Gamma slot) and the per-pass scratch, reserved once and
+  // reused
   struct Build {
-    const std::vector<qdc_plan_op>& plan;
-    bool backward;
-    size_t first_inject;
-    const Flat &cg, &vg;
-    const std::vector<size_t>& gidx;
-    const std::vector<uint32_t>& var_idx;
-    const std::vector<uint32_t>& out_idx;
-    const Flat* dg;
+    Call& c;
     fop* fops;
     cx* mats;
     size_t fo, mo;
@@ -1101,32 +1088,27 @@ struct Circuit {
   // applied matrices, B = product of the bwd pull-backs) in one pinned buffer, then upload it.
   // backward: `first_inject` = plan index of the first cotangent injection (passes before it
   // only uncompute fwd); gradient stages get slots nvar, nvar+1, ... of the gradient buffer and
-  // a recipe in stage_post (qdc_stage.hpp).
+  // a recipe in c.stage_post (qdc_stage.hpp).
   // forward: densities reduce into dens slot out_idx[instr]; backward: injections read their
   // cotangent from dg.
-  const char* build_program(std::vector<Item>& items, const std::vector<qdc_plan_op>& plan,
-                            bool backward, size_t first_inject, const Flat& cg, const Flat& vg,
-                            const std::vector<size_t>& gidx, size_t& mats_off,
-                            const std::vector<uint32_t>& var_idx, uint32_t nvar,
-                            const std::vector<uint32_t>& out_idx, const Flat* dg) {
-    stage_post.clear();
+  const char* build_program(Call& c) {
+    std::vector<Item>& items = c.items;
     if (spec_cache.size() >= 4096 && !dry) spec_cache.clear();  // bounded; items of this call point into it
     size_t nops = 0;
     for (const Item& it : items)
-      if (it.type == 2) nops += it.stages.size();
+      if (it.type == ITEM_FUSED) nops += it.stages.size();
     if (nops == 0) return nullptr;
-    QDC_TRY(reserve_program(nops, items.size(), mats_off));
-    Build B{plan, backward, first_inject, cg, vg, gidx, var_idx, out_idx, dg,
-            reinterpret_cast<fop*>(prog_host), reinterpret_cast<cx*>(prog_host + mats_off), 0, 0,
-            nvar, {}, {}, {}, {}, {}};
+    QDC_TRY(reserve_program(nops, items.size(), c.mats_off));
+    Build B{c, reinterpret_cast<fop*>(prog_host), reinterpret_cast<cx*>(prog_host + c.mats_off), 0, 0,
+            c.nvar, {}, {}, {}, {}, {}};
     B.ops.reserve(k.fuse_max_ops);
     B.gates.reserve(k.fuse_max_ops);
     B.rs.reserve(k.fuse_max_ops);
     B.sst.reserve(2 * (size_t)k.fuse_max_ops + 1);
     for (size_t ii = 0; ii < items.size(); ++ii) {
       Item& it = items[ii];
-      if (it.type != 2) continue;
-      const bool two = backward && it.ops[0] >= first_inject;
+      if (it.type != ITEM_FUSED) continue;
+      const bool two = c.two_state(it);
       QDC_TRY(build_stages(B, it, ii, two));
       QDC_TRY(classify_pass(B, it, two));
       if (it.rq)
@@ -1142,7 +1124,7 @@ struct Circuit {
     }
     for (auto& d : devs) {  // prog_host is not rewritten before the call's final sync
       QDC_TRY(d->ctx.use());
-      QDC_HIP(hipMemcpyAsync(d->prog_dev, prog_host, mats_off + B.mo * sizeof(cx),
+      QDC_HIP(hipMemcpyAsync(d->prog_dev, prog_host, c.mats_off + B.mo * sizeof(cx),
                              hipMemcpyHostToDevice, d->ctx.stream));
     }
     return spec_load(items);
@@ -1194,18 +1176,18 @@ struct Circuit {
     it.has_red = false;
     it.writes_f = false;
     B.ops.clear();
-    if (rec_mats) (*rec_mats)[ii].clear();
-    const FusionPlanner PL = planner();
+    const Call& c = B.c;
+    const FusionPlanner& PL = c.P;
     for (size_t sj = 0; sj < it.stages.size(); ++sj) {
       const auto& st = it.stages[sj];
       StageOp so{fop{}, 0, 0, -1};
       for (uint32_t pi : st) {
-        so.q |= (1ull << B.plan[pi].pos2) | (1ull << B.plan[pi].pos1);
-        so.cls |= PL.op_class(B.plan[pi], B.backward);
+        so.q |= (1ull << c.plan[pi].pos2) | (1ull << c.plan[pi].pos1);
+        so.cls |= PL.op_class(c.plan[pi], c.backward);
       }
       B.ops.push_back(so);
-      if (PL.is_meas(B.plan[st[0]]))
-        measure_stage(B, it, ii, B.plan[st[0]]);
+      if (PL.is_meas(c.plan[st[0]]))
+        measure_stage(B, it, ii, c.plan[st[0]]);
       else
         QDC_TRY(gate_stage(B, it, ii, sj, two));
     }
@@ -1213,7 +1195,7 @@ struct Circuit {
   }
   // a density (forward) or a cotangent injection (backward)
   void measure_stage(Build& B, Item& it, size_t ii, const qdc_plan_op& op) {
-    if (rec_mats) (*rec_mats)[ii].push_back(smat_identity(2));
+    if (B.c.record) B.c.stage_mats[ii].push_back(smat_identity(2));
     const bool q1 = is_q1_density(ins[op.instr].kind);
     const int R = q1 ? 2 : 4;
     fop& F = B.ops.back().F;
@@ -1222,9 +1204,9 @@ struct Circuit {
     F.mat = (uint32_t)B.mo;
     cx* m = B.mats + B.mo;
     for (int i = 0; i < 2 * R * R; ++i) m[i] = cx{0, 0};
-    if (B.backward) {  // b += (G^T on pos) (2 conj f), G = conj of the JAX cotangent
+    if (B.c.backward) {  // b += (G^T on pos) (2 conj f), G = conj of the JAX cotangent
       F.kind = q1 ? FK_INJ1 : FK_INJ2;
-      const qdc_complex* gd = B.dg->at(B.gidx[op.instr]);
+      const qdc_complex* gd = B.c.dg->at(B.c.gidx[op.instr]);
       if (q1) {
         const mat<2> t = transpose<2>(to_mat<2>(gd));
         for (int i = 0; i < 4; ++i) m[i] = t.a[i];
@@ -1234,7 +1216,7 @@ struct Circuit {
       }
     } else {
       F.kind = q1 ? FK_DENS1 : FK_DENS2;
-      it.grad_slots.push_back(B.out_idx[op.instr]);
+      it.grad_slots.push_back(B.c.out_idx[op.instr]);
       it.has_red = true;
     }
     it.flops_per_amp += 8.0 * (q1 ? 2.0 : 4.0);
@@ -1243,6 +1225,7 @@ struct Circuit {
   // a stage of gates: compose it (qdc_stage.hpp), take the forward's adjoint where the pass
   // mirrors one, record it for the trace, write its matrices A and B
   const char* gate_stage(Build& B, Item& it, size_t ii, size_t sj, bool two) {
+    Call& c = B.c;
     const auto& st = it.stages[sj];
     // stage qubits (physical positions), lo < hi
     const uint64_t qm = B.ops.back().q;
@@ -1252,11 +1235,10 @@ struct Circuit {
     bool any_grad = false;
     B.gates.clear();
     for (uint32_t pi : st) {
-      const qdc_plan_op& op = B.plan[pi];
+      const qdc_plan_op& op = c.plan[pi];
       const Instr& in = ins[op.instr];
       GateMats M;
-      QDC_TRY(gate_mats(in.kind, is_const(in.kind) ? B.cg.at(B.gidx[op.instr]) : B.vg.at(B.gidx[op.instr]),
-                        B.backward, M));
+      QDC_TRY(gate_mats(in.kind, c.gate(in, op.instr), c.backward, M));
       B.gates.emplace_back();
       StageGateIn& g = B.gates.back();
       for (int i = 0; i < M.count(); ++i) {
@@ -1266,7 +1248,7 @@ struct Circuit {
       g.diag = M.diag;
       g.role = stage_role(R, is_q1_gate(in.kind), op.pos2, lo, hi);
       const bool grad = two && is_var(in.kind);
-      g.var = grad ? (int)B.var_idx[op.instr] : -1;
+      g.var = grad ? (int)c.var_idx[op.instr] : -1;
       any_grad = any_grad || grad;
     }
     SMat A;
@@ -1274,11 +1256,11 @@ struct Circuit {
     StagePost post;
     stage_compose(B.gates.data(), B.gates.size(), R, A, Bp, post);
     const bool all_diag = post.diag_only;
-    if (rec_mats) (*rec_mats)[ii].push_back(A);  // the forward's matrix, its own frame
+    if (c.record) c.stage_mats[ii].push_back(A);  // the forward's matrix, its own frame
     SMat Aup = A;
-    const bool from_fwd = B.backward && mirror_adjoint(B.plan, it, sj, R, Aup);
+    const bool from_fwd = c.backward && mirror_adjoint(c.plan, it, sj, R, Aup);
     if (tracing) {  // (physical positions; trace_logical maps them to logical qubits)
-      TraceOp t{B.backward ? 1u : 0u, (uint32_t)ii, hi, lo, (uint32_t)R, all_diag ? 1u : 0u,
+      TraceOp t{c.backward ? 1u : 0u, (uint32_t)ii, hi, lo, (uint32_t)R, all_diag ? 1u : 0u,
                 from_fwd ? 1u : 0u, 0u, {}};
       for (int i = 0; i < R * R; ++i) {
         const bool keep = !all_diag || i % (R + 1) == 0;
@@ -1311,7 +1293,7 @@ struct Circuit {
       it.grad_slots.push_back(post.slot);
       B.ops.back().slot = (int)post.slot;
       it.has_red = true;
-      stage_post.push_back(std::move(post));
+      c.stage_post.push_back(std::move(post));
     }
     return nullptr;
   }
@@ -1401,7 +1383,7 @@ struct Circuit {
     QDC_TRY(rq_variant(two, it.tbits, it.var));
     const RqVariant& V = *it.var;
     const RqPlan& P = rq_plan_cached(B.rs, it.tbits, perm ? src : nullptr, k.rq_maxcl != 0, V.ns,
-                                     rq_keep(V));
+                                     rq_keep(V, k.spec_half != 0));
     it.l0 = put_layout(B, P.load, it.tbits);
     {  // rqio after the load descriptor
       rqio io{};
@@ -1433,17 +1415,15 @@ struct Circuit {
         const int slot = B.ops[step.stage].slot;
         if (slot >= 0) it.grad_slots.push_back((uint32_t)slot);
         F = B.ops[step.stage].F;
-        F.t1 = step.cs;
         F.t2 = 0;
-        // two-qubit / diagonal stages run with the lower slot first (half the kernel's
-        // cases): exchange t1 and t2 by permuting the matrices' index bits, and the
-        // stage's Gamma back on the host
-        const uint32_t kd = F.kind & 7u;
-        if ((kd == FK_Q2 || kd == FK_DIAG) && (step.cs >> 3) > (step.cs & 7u)) {
-          F.t1 = (step.cs & 7u) * 8u + (step.cs >> 3);
-          stage_swap_slots(&B.mats[F.mat], kd == FK_DIAG);
+        // the canonical slot case (rq_slot_case): where it exchanged the slots, exchange them
+        // in the matrices by permuting their index bits, and the stage's Gamma back on the host
+        bool swapped = false;
+        F.t1 = rq_slot_case(F.kind, step.cs, swapped);
+        if (swapped) {
+          stage_swap_slots(&B.mats[F.mat], (F.kind & 7u) == FK_DIAG);
           if (slot >= 0)
-            for (StagePost& sp : stage_post)
+            for (StagePost& sp : B.c.stage_post)
               if (sp.slot == (uint32_t)slot) sp.swapped = true;
         }
         if (spec) B.sst.push_back(SpecStep{false, lcur, lcur, F});
@@ -1467,7 +1447,7 @@ struct Circuit {
   // source is generated once per distinct program (per process): the key is everything it
   // depends on, the layouts, stage kinds, slot cases and Gamma flags
   SpecEntry* spec_entry(Build& B, const RqVariant& V, uint32_t tbits, const RqLayout& load) {
-    const bool half = V.pass_half && k.spec_half && !spec_imm() && spec_half_ok(B.sst);
+    const bool half = spec_half_buffer(V, k.spec_half != 0, B.sst);
     std::vector<uint32_t>& key = B.key;
     key.assign({(uint32_t)(&V - rq_variants()), tbits, spec_imm() ? 1u : 0u, half ? 1u : 0u});
     auto put_layout_key = [&](const RqLayout& L) {
@@ -1486,14 +1466,8 @@ struct Circuit {
       }
     }
     auto hit = spec_cache.find(key);
-    if (hit == spec_cache.end()) {
-      const SpecKind K = spec_kind(V, half);
-      const std::string body = spec_program_source(B.sst, tbits, K);
-      SpecEntry e;
-      e.name = spec_kernel_name(body, K);
-      e.src = spec_kernel_source(e.name, body, K);
-      hit = spec_cache.emplace(key, std::move(e)).first;
-    }
+    if (hit == spec_cache.end())
+      hit = spec_cache.emplace(key, spec_kernel_of(B.sst, V, tbits, half)).first;
     return &hit->second;
   }
   // specialized passes: circuits of >= spec_min_qubits local qubits (every shard runs the same
@@ -1555,26 +1529,33 @@ struct Circuit {
     auto f = it.spec->fn.find(dev);
     return f == it.spec->fn.end() ? nullptr : f->second;
   }
+  // What a fused launch used, handed back to run_fused, which commits the pass's reduction
+  // slots with it
+  struct GridUse {
+    uint32_t grid = 0;  // the blocks launched (size_grid's input: the resident blocks)
+    uint32_t ndyn = 0;  // granule partials per slot
+  };
   // Run one fused group on every shard.  grads != nullptr: two-state reverse program whose
   // gradient gates write partials for gradient buffer rows var_idx[...].
   template <bool TWO, bool HASRED, bool WF>
   const char* launch_fused(Ctx& ctx, const char* name, double bytes, const fgeo& fg, chunk* f,
                            chunk* b, const fop* fops, const cx* mats, cx* partials,
-                           uint64_t stride) {
+                           uint64_t stride, GridUse& use) {
     // one-state passes on the smaller tile (QDC_TILE1_CHUNKS = TILE_CHUNKS_2): the LDS kernel
     // of that tile size (a k_fused tile is always TB chunks)
     if constexpr (!TWO) {
       if ((1ull << (fg.lc + fg.h)) == TILE_CHUNKS_2)
         return launch_fused_tb<TWO, HASRED, WF, (int)TILE_CHUNKS_2>(ctx, name, bytes, fg, f, b, fops,
-                                                                    mats, partials, stride);
+                                                                    mats, partials, stride, use);
     }
     constexpr int TB = TWO ? (int)TILE_CHUNKS_2 : (int)TILE_CHUNKS_1;
-    return launch_fused_tb<TWO, HASRED, WF, TB>(ctx, name, bytes, fg, f, b, fops, mats, partials, stride);
+    return launch_fused_tb<TWO, HASRED, WF, TB>(ctx, name, bytes, fg, f, b, fops, mats, partials, stride,
+                                                use);
   }
   template <bool TWO, bool HASRED, bool WF, int TB>
   const char* launch_fused_tb(Ctx& ctx, const char* name, double bytes, const fgeo& fg, chunk* f,
                               chunk* b, const fop* fops, const cx* mats, cx* partials,
-                              uint64_t stride) {
+                              uint64_t stride, GridUse& use) {
     if ((1ull << (fg.lc + fg.h)) != (uint64_t)TB)
       return fail("internal: a %llu-chunk fused tile on the %d-chunk LDS kernel",
                   (unsigned long long)(1ull << (fg.lc + fg.h)), TB);
@@ -1582,23 +1563,22 @@ struct Circuit {
     // occupancy 2 was 2-4 % slower)
     constexpr int NT = 256;
     auto kern = k_fused<TWO, TB, HASRED, WF, NT>;
-    uint32_t grid = 0;
-    QDC_TRY(fused_grid((const void*)kern, nullptr, NT, grid));
+    QDC_TRY(fused_grid((const void*)kern, nullptr, NT, use.grid));
     fgeo g = fg;
-    QDC_TRY(size_grid(ctx, g, grid, false, "fused"));
-    return ctx.launch_block(name, bytes, kern, grid, (uint32_t)NT, f, b, fops, mats, g, partials,
+    QDC_TRY(size_grid(ctx, g, use, false, "fused"));
+    return ctx.launch_block(name, bytes, kern, use.grid, (uint32_t)NT, f, b, fops, mats, g, partials,
                             stride);
   }
   // a density-only pass (k_dens1): the tile of the one-state LDS kernel of its size
   const char* launch_dens1(Ctx& ctx, const char* name, double bytes, const fgeo& fg, chunk* f,
-                           const fop* fops, cx* partials, uint64_t stride) {
+                           const fop* fops, cx* partials, uint64_t stride, GridUse& use) {
     if ((1ull << (fg.lc + fg.h)) == TILE_CHUNKS_2)
-      return launch_dens1_tb<(int)TILE_CHUNKS_2>(ctx, name, bytes, fg, f, fops, partials, stride);
-    return launch_dens1_tb<(int)TILE_CHUNKS_1>(ctx, name, bytes, fg, f, fops, partials, stride);
+      return launch_dens1_tb<(int)TILE_CHUNKS_2>(ctx, name, bytes, fg, f, fops, partials, stride, use);
+    return launch_dens1_tb<(int)TILE_CHUNKS_1>(ctx, name, bytes, fg, f, fops, partials, stride, use);
   }
   template <int TB>
   const char* launch_dens1_tb(Ctx& ctx, const char* name, double bytes, const fgeo& fg, chunk* f,
-                              const fop* fops, cx* partials, uint64_t stride) {
+                              const fop* fops, cx* partials, uint64_t stride, GridUse& use) {
     if ((1ull << (fg.lc + fg.h)) != (uint64_t)TB)
       return fail("internal: a %llu-chunk density tile on the %d-chunk kernel",
                   (unsigned long long)(1ull << (fg.lc + fg.h)), TB);
@@ -1606,11 +1586,10 @@ struct Circuit {
       return fail("internal: a density pass of %u ops, %u reductions", fg.nops, fg.ngrad);
     constexpr int NT = 256;
     auto kern = k_dens1<TB, NT>;
-    uint32_t grid = 0;
-    QDC_TRY(fused_grid((const void*)kern, nullptr, NT, grid));
+    QDC_TRY(fused_grid((const void*)kern, nullptr, NT, use.grid));
     fgeo g = fg;
-    QDC_TRY(size_grid(ctx, g, grid, false, "density"));  // (ngrad = nops > 0: always a reduction)
-    return ctx.launch_block(name, bytes, kern, grid, (uint32_t)NT, (const chunk*)f, fops, g,
+    QDC_TRY(size_grid(ctx, g, use, false, "density"));  // (ngrad = nops > 0: always a reduction)
+    return ctx.launch_block(name, bytes, kern, use.grid, (uint32_t)NT, (const chunk*)f, fops, g,
                             partials, stride);
   }
   // register-resident pass (qdc_rq.hpp) on its kernel variant V (emit_rq_pass's choice,
@@ -1619,7 +1598,7 @@ struct Circuit {
   const char* launch_rq(Ctx& ctx, const char* name, double bytes, const fgeo& fg, bool two,
                         uint32_t tbits, const RqVariant* V, uint32_t l0, chunk* f, chunk* b,
                         const fop* fops, const cx* mats, cx* partials, uint64_t stride,
-                        hipFunction_t spec = nullptr) {
+                        hipFunction_t spec, GridUse& use) {
     if (!V || V->two != two || V->tbits != tbits || (spec && !V->prefix))
       return fail("internal: a register-resident pass without its kernel variant");
     // a register-resident pass holds gate stages only (classify_pass), and only two-state
@@ -1627,15 +1606,14 @@ struct Circuit {
     // partials) and the one-state kernels (no reduction code) rest on that.
     if (!two && fg.ngrad > 0)
       return fail("internal: a one-state register-resident pass with %u reductions", fg.ngrad);
-    uint32_t grid = 0;
     QDC_TRY(fused_grid((const void*)V->kernel, spec && V->own_grid ? spec : nullptr, (int)V->threads,
-                       grid));
+                       use.grid));
     fgeo g = fg;
-    QDC_TRY(size_grid(ctx, g, grid, V->dyn, "fused"));
+    QDC_TRY(size_grid(ctx, g, use, V->dyn, "fused"));
     if (spec)
-      return ctx.launch_module(name, bytes, spec, grid, V->threads, f, b, fops, mats, g, l0, partials,
-                               stride);
-    return ctx.launch_block(name, bytes, V->kernel, grid, V->threads, f, b, fops, mats, g, l0,
+      return ctx.launch_module(name, bytes, spec, use.grid, V->threads, f, b, fops, mats, g, l0,
+                               partials, stride);
+    return ctx.launch_block(name, bytes, V->kernel, use.grid, V->threads, f, b, fops, mats, g, l0,
                             partials, stride);
   }
   // One wave of resident blocks of a kernel (occupancy query, cached per kernel), or
@@ -1666,8 +1644,9 @@ struct Circuit {
   // The tile shares of a fused launch over g.ntiles tiles, from `grid` resident blocks: static
   // shares + a dynamic tail where the kernel takes one (dyn) and Ctx::plan_dyn finds one, else a
   // power-of-two number of tiles per block on the fewest blocks that need.  Sets g's shares and
-  // `grid`, and records the launch's grid and granule partials for the reduction slots' commit.
-  const char* size_grid(Ctx& ctx, fgeo& g, uint32_t& grid, bool dyn, const char* what) {
+  // hands back the launch's grid and granule partials (GridUse).
+  const char* size_grid(Ctx& ctx, fgeo& g, GridUse& use, bool dyn, const char* what) {
+    uint32_t& grid = use.grid;
     if (!(dyn && grid >= 8 && g.ntiles >= 4ull * grid && ctx.plan_dyn(g, grid))) {
       uint64_t tpb = 1;
       while (tpb * grid < g.ntiles) tpb <<= 1;
@@ -1675,14 +1654,13 @@ struct Circuit {
       grid = (uint32_t)((g.ntiles + tpb - 1) / tpb);
     }
     if (g.ngrad > 0 && grid > NBMAX) return fail("%s reduction grid %u exceeds %u", what, grid, NBMAX);
-    last_fused_grid = grid;
-    last_fused_ndyn = g.ndyn ? ctx.last_ndyn : 0u;
+    use.ndyn = g.ndyn ? ctx.last_ndyn : 0u;
     return nullptr;
   }
 
   // Run one fused pass on every shard.  two: fwd and bwd (reverse sweep).  Reductions (Gamma
   // stages, densities) go to slots it.grad_slots of red_base (grads or dens of each shard).
-  const char* run_fused(const Item& it, bool two, size_t mats_off, bool red_to_grads) {
+  const char* run_fused(const Call& c, const Item& it, bool two) {
     fgeo fg{};
     fg.order = it.rq ? (uint32_t)k.rq_order : 0u;
     fg.gm = gm;
@@ -1704,12 +1682,12 @@ struct Circuit {
       Ctx& ctx = s.c();
       QDC_TRY(ctx.use());
       const fop* fops = reinterpret_cast<const fop*>(s.d->prog_dev + it.fop_off);
-      const cx* mats = reinterpret_cast<const cx*>(s.d->prog_dev + mats_off);
+      const cx* mats = reinterpret_cast<const cx*>(s.d->prog_dev + c.mats_off);
       chunk* f = reinterpret_cast<chunk*>(s.state);
       chunk* b = reinterpret_cast<chunk*>(s.bwd);
       cx* parts = nullptr;
       if (fg.ngrad > 0) {
-        cx* base = red_to_grads ? s.grads : s.dens;
+        cx* base = c.backward ? s.grads : s.dens;
         QDC_TRY(ctx.begin_reduction(base, 0));
         if (ctx.pending_dst.size() + fg.ngrad > (size_t)FIN_MAX) QDC_TRY(ctx.flush());
         ctx.pending_base = base;
@@ -1718,32 +1696,30 @@ struct Circuit {
       }
       const uint64_t stride = (uint64_t)NBMAX * RED;
       ctx.next_flops = flops;
+      GridUse use;
       if (it.rq) {
         QDC_TRY(launch_rq(ctx, name, bytes, fg, two, it.tbits, it.var, it.l0, f, b, fops, mats, parts,
-                          stride, spec_fn_on(it, ctx.device)));
+                          stride, spec_fn_on(it, ctx.device), use));
       } else if (two) {
         if (it.writes_f)
-          QDC_TRY((launch_fused<true, true, true>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride)));
+          QDC_TRY((launch_fused<true, true, true>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride, use)));
         else
-          QDC_TRY((launch_fused<true, false, false>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride)));
+          QDC_TRY((launch_fused<true, false, false>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride, use)));
       } else if (it.dens1) {
-        QDC_TRY(launch_dens1(ctx, name, bytes, fg, f, fops, parts, stride));
+        QDC_TRY(launch_dens1(ctx, name, bytes, fg, f, fops, parts, stride, use));
       } else if (!it.has_red) {
-        QDC_TRY((launch_fused<false, false, true>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride)));
+        QDC_TRY((launch_fused<false, false, true>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride, use)));
       } else if (it.writes_f) {
-        QDC_TRY((launch_fused<false, true, true>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride)));
+        QDC_TRY((launch_fused<false, true, true>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride, use)));
       } else {
-        QDC_TRY((launch_fused<false, true, false>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride)));
+        QDC_TRY((launch_fused<false, true, false>(ctx, name, bytes, fg, f, b, fops, mats, parts, stride, use)));
       }
       if (fg.ngrad > 0)
-        for (uint32_t slot : it.grad_slots) ctx.commit(slot, last_fused_grid, last_fused_ndyn);
+        for (uint32_t slot : it.grad_slots) ctx.commit(slot, use.grid, use.ndyn);
     }
-    // a permuting pass stored its tile's qubits at new positions (later ops were planned so)
-    for (const auto& sw : it.swaps) layout.swap_phys(sw.first, sw.second);
     return nullptr;
   }
 
-  // --- forward (Circuit::run / Circuit::forward) --------------------------------------------
   // one gate on one state: forward, or (uncompute) the reverse sweep before its first cotangent
   const char* apply_gate(Ctx& ctx, const Instr& in, const qdc_complex* g4, cx* s, uint32_t p2,
                          uint32_t p1, bool uncompute) {
@@ -1760,39 +1736,30 @@ struct Circuit {
   }
 
   // The trace entries of this call's fused stages (gate_stage, physical positions) mapped to
-  // logical qubits by replaying the call's layout changes (remaps, undone remaps, permuting
-  // passes' swaps) from `layout` (the call's start), with the single-gate items' matrices (as
-  // apply_gate / reverse_dense apply them) inserted in item order.  Dry runs only.
-  const char* trace_logical(const std::vector<Item>& items, const std::vector<qdc_plan_op>& pl,
-                            bool backward, const Flat& cg, const Flat& vg,
-                            const std::vector<size_t>& gidx) {
-    std::vector<TraceOp> fused(trace.begin() + (std::ptrdiff_t)trace_from, trace.end());
-    trace.resize(trace_from);
+  // logical qubits by replaying the call's layout changes (step_layout) from `layout` (the
+  // call's start), with the single-gate items' matrices (as apply_gate / reverse_dense apply
+  // them) inserted in item order.  Dry runs only.
+  const char* trace_logical(const Call& c) {
+    std::vector<TraceOp> fused(trace.begin() + (std::ptrdiff_t)c.trace_start, trace.end());
+    trace.resize(c.trace_start);
     QubitMap m = layout;
     size_t t = 0;
-    for (size_t ii = 0; ii < items.size(); ++ii) {
-      const Item& it = items[ii];
+    for (size_t ii = 0; ii < c.items.size(); ++ii) {
+      const Item& it = c.items[ii];
       for (; t < fused.size() && fused[t].item == ii; ++t) {
         TraceOp s = fused[t];
         s.q2 = m.logi[s.q2];
         s.q1 = m.logi[s.q1];
         trace.push_back(s);
       }
-      if (it.type == 1) {
-        const qdc_plan_op& op = pl[it.ops[0]];
-        if (it.inv)
-          m.unapply(op.victims);
-        else
-          m.apply(op.victims);
-      } else if (it.type == 0) {
-        const qdc_plan_op& op = pl[it.ops[0]];
+      if (it.type == ITEM_OP) {
+        const qdc_plan_op& op = c.plan[it.ops[0]];
         const Instr& in = ins[op.instr];
         if (is_const(in.kind) || is_var(in.kind)) {
-          const qdc_complex* g4 = is_const(in.kind) ? cg.at(gidx[op.instr]) : vg.at(gidx[op.instr]);
-          TraceOp s{backward ? 1u : 0u, (uint32_t)ii, m.logi[op.pos2], m.logi[op.pos1], 4u,
+          TraceOp s{c.backward ? 1u : 0u, (uint32_t)ii, m.logi[op.pos2], m.logi[op.pos1], 4u,
                     is_diag(in.kind) ? 1u : 0u, 0u, 1u, {}};
           GateMats M;
-          QDC_TRY(gate_mats(in.kind, g4, backward, M));
+          QDC_TRY(gate_mats(in.kind, c.gate(in, op.instr), c.backward, M));
           s.R = (uint32_t)M.R;
           if (M.R == 2) s.q1 = s.q2;
           for (int i = 0; i < M.count(); ++i)  // (a diagonal expanded)
@@ -1800,9 +1767,8 @@ struct Circuit {
           trace.push_back(s);
         }
       }
-      for (const auto& sw : it.swaps) m.swap_phys(sw.first, sw.second);
+      step_layout(m, it, c.plan);
     }
-    trace_from = trace.size();
     return nullptr;
   }
 
@@ -1813,14 +1779,93 @@ struct Circuit {
     }
     return nullptr;
   }
+
+  // --- the sweep: one loop over a call's items, forward or reverse ------------------------------
+  // One plan op outside the fused passes, on every shard.  A gate: applied (forward), only
+  // uncomputed on fwd (reverse sweep before its first cotangent), or reversed on the state pair
+  // with its gradient.  A density: measured (forward), or its cotangent injected (backward).
+  const char* run_single(Call& c, const qdc_plan_op& op) {
+    const Instr& in = ins[op.instr];
+    const bool gate = is_const(in.kind) || is_var(in.kind), var = is_var(in.kind);
+    const bool q1 = is_q1_density(in.kind);
+    const qdc_complex* g4 = gate ? c.gate(in, op.instr) : c.backward ? c.dg->at(c.gidx[op.instr]) : nullptr;
+    for (auto& s : sh) {
+      Ctx& ctx = s.c();
+      QDC_TRY(ctx.use());
+      if (gate && !c.have_bwd)
+        QDC_TRY(apply_gate(ctx, in, g4, s.state, op.pos2, op.pos1, c.backward));
+      else if (gate)
+        QDC_TRY(reverse_gate(ctx, in, g4, s.state, s.bwd, op.pos2, op.pos1, var ? s.grads : nullptr,
+                             c.var_idx[op.instr]));
+      else if (!c.backward && q1)
+        QDC_TRY(density<2>(ctx, s.state, op.pos2, op.pos2, nl, s.dens, c.out_idx[op.instr], 0));
+      else if (!c.backward)
+        QDC_TRY(density<4>(ctx, s.state, op.pos2, op.pos1, nl, s.dens, c.out_idx[op.instr], 0));
+      else if (q1)
+        QDC_TRY(inject<2>(ctx, s.state, s.bwd, transpose<2>(to_mat<2>(g4)), op.pos2, op.pos2, nl,
+                          !c.have_bwd));
+      else
+        QDC_TRY(inject<4>(ctx, s.state, s.bwd, transpose<4>(to_mat<4>(g4)), op.pos2, op.pos1, nl,
+                          !c.have_bwd));
+    }
+    if (!gate && c.backward) c.have_bwd = true;
+    return nullptr;
+  }
+  // a run of diagonal cotangent injections: one elementwise pass (no pass program)
+  const char* run_diag_inject(Call& c, const Item& item) {
+    diag_tab T;
+    const uint32_t ng = diag_table(c, item, T);
+    for (auto& s : sh) {
+      QDC_TRY(s.c().use());
+      QDC_TRY(qdc::diag_inject(s.c(), s.state, s.bwd, T, ng, nl, gm, c.have_bwd));
+    }
+    c.have_bwd = true;
+    return nullptr;
+  }
+  const char* run_item(Call& c, const Item& item) {
+    switch (item.type) {
+      case ITEM_DIAG_INJECT:
+        return run_diag_inject(c, item);
+      case ITEM_FUSED: {
+        const bool two = c.two_state(item);
+        if (two && !c.have_bwd) {  // the first injection is fused: it adds into a zero bwd
+          for (auto& s : sh) {
+            QDC_TRY(s.c().use());
+            QDC_TRY(zero_bwd(s));
+          }
+          c.have_bwd = true;
+        }
+        return run_fused(c, item, two);
+      }
+      case ITEM_REMAP:
+        return remap(c.plan[item.ops[0]], item.inv, c.have_bwd);
+      default:
+        return run_single(c, c.plan[item.ops[0]]);
+    }
+  }
+  // The call's items from `from` on: each run (a dry run launches nothing), then the layout it
+  // leaves
+  const char* run_items(Call& c, size_t from = 0) {
+    for (size_t ii = from; ii < c.items.size(); ++ii) {
+      if (!dry) QDC_TRY(run_item(c, c.items[ii]));
+      step_layout(layout, c.items[ii], c.plan);
+    }
+    return nullptr;
+  }
+  // the program built and (a dry, traced run) the call's trace entries made logical
+  const char* build_and_trace(Call& c, const char* what) {
+    QDC_TRY(build_program(c));
+    c.ht[3] = hclock::now();
+    if (k.rq_stats) fprintf(stderr, "%s plan+build %.3f ms\n", what, ms_between(c.ht[2], c.ht[3]));
+    return dry && tracing ? trace_logical(c) : nullptr;
+  }
+
+  // --- forward (Circuit::run / Circuit::forward) --------------------------------------------
   const char* execute(int mode, const Flat& cg, const Flat& vg, qdc_complex* out) {
-    hclock::time_point ht[6];
-    ht[0] = hclock::now();
-    std::vector<size_t> gidx;
-    QDC_TRY(validate_forward(cg, vg, gidx));
-    std::vector<uint32_t> out_idx;
+    Call c(*this, mode, false, mode == QDC_MODE_FORWARD, &cg, &vg);
+    QDC_TRY(validate_forward(cg, vg, c.gidx));
     std::vector<int> widths;
-    outputs(mode, out_idx, widths);
+    outputs(mode, c.out_idx, widths);
     const size_t nout = widths.size();
     if (!dry) {
       QDC_TRY(dyn_reset_all());
@@ -1832,75 +1877,33 @@ struct Circuit {
       QDC_TRY(s.c().use());
       QDC_TRY(copy_initial(s));
     }
-    mark_inexact(cg, vg, gidx);
-    ht[1] = hclock::now();
-    std::vector<qdc_plan_op> pl = plan(mode);
-    sched_mirror = mode == QDC_MODE_FORWARD;
-    std::vector<Item> items = schedule(pl, false, SIZE_MAX);
-    ht[2] = hclock::now();
-    size_t mats_off = 0;
-    const auto tb0 = std::chrono::steady_clock::now();
+    mark_inexact(cg, vg, c.gidx);
+    c.ht[1] = hclock::now();
+    c.plan = plan(mode);
+    schedule(c);
+    c.ht[2] = hclock::now();
     // a mirrored forward records what its backward will undo (forward mode only)
     mrec.valid = false;
-    const bool record = mirror_on() && mode == QDC_MODE_FORWARD;
-    std::vector<std::vector<SMat>> mats_rec(record ? items.size() : 0);
-    rec_mats = record ? &mats_rec : nullptr;
-    const char* berr = build_program(items, pl, false, 0, cg, vg, gidx, mats_off, {}, 0, out_idx, nullptr);
-    rec_mats = nullptr;
-    QDC_TRY(berr);
-    ht[3] = hclock::now();
-    if (record) mrec.capture(cg, vg, pl, items, std::move(mats_rec), inexact);
-    if (k.rq_stats)
-      fprintf(stderr, "forward plan+build %.3f ms\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count());
-    if (dry) {  // the layout the passes leave (permuting passes' swaps, remaps), no launch
-      if (tracing) QDC_TRY(trace_logical(items, pl, false, cg, vg, gidx));
-      for (const Item& item : items) {
-        for (const auto& sw : item.swaps) layout.swap_phys(sw.first, sw.second);
-        if (item.type == 1) layout.apply(pl[item.ops[0]].victims);
-      }
-      if (record) {
-        mrec.end_phys = layout.phys;
-        mrec.valid = true;
-      }
-      return nullptr;
+    c.record = mirror_on() && mode == QDC_MODE_FORWARD;
+    c.stage_mats.resize(c.record ? c.items.size() : 0);
+    QDC_TRY(build_and_trace(c, "forward"));
+    if (c.record) mrec.capture(cg, vg, c.plan, c.items, std::move(c.stage_mats), inexact);
+    QDC_TRY(run_items(c));
+    if (!dry) {
+      c.ht[4] = hclock::now();
+      QDC_TRY(flush_all());
     }
-    for (const Item& item : items) {
-      if (item.type == 2) {
-        QDC_TRY(run_fused(item, false, mats_off, false));
-        continue;
-      }
-      const qdc_plan_op& op = pl[item.ops[0]];
-      if (op.type == QDC_PLAN_REMAP) {
-        QDC_TRY(remap(op, false));
-        continue;
-      }
-      const Instr& in = ins[op.instr];
-      for (auto& s : sh) {
-        Ctx& ctx = s.c();
-        QDC_TRY(ctx.use());
-        if (is_const(in.kind) || is_var(in.kind)) {
-          const qdc_complex* g4 = is_const(in.kind) ? cg.at(gidx[op.instr]) : vg.at(gidx[op.instr]);
-          QDC_TRY(apply_gate(ctx, in, g4, s.state, op.pos2, op.pos1, false));
-        } else if (is_q1_density(in.kind)) {
-          QDC_TRY(density<2>(ctx, s.state, op.pos2, op.pos2, nl, s.dens, out_idx[op.instr], 0));
-        } else {
-          QDC_TRY(density<4>(ctx, s.state, op.pos2, op.pos1, nl, s.dens, out_idx[op.instr], 0));
-        }
-      }
-    }
-    ht[4] = hclock::now();
-    QDC_TRY(flush_all());
-    if (record) {  // (valid once every pass ran; the backward starts from this layout)
+    if (c.record) {  // (valid once every pass ran; the backward starts from this layout)
       mrec.end_phys = layout.phys;
       mrec.valid = true;
     }
+    if (dry) return nullptr;
     std::vector<cx*> bufs;
     for (auto& s : sh) bufs.push_back(s.dens);
     QDC_TRY(ex.allreduce(sh, bufs, nout * RED));
     QDC_TRY(collect(sh[0].dens, widths, out));
-    ht[5] = hclock::now();
-    host_record(0, ht);
+    c.ht[5] = hclock::now();
+    host_record(0, c.ht);
     return nullptr;
   }
 
@@ -1930,57 +1933,55 @@ struct Circuit {
 
   // --- diagonal cotangent injections ----------------------------------------------------------
   // the injection's diagonal (G^T on its qubits has the diagonal of G), or false
-  bool diag_cotangent(const qdc_plan_op& op, const Flat& dg, const std::vector<size_t>& gidx) const {
+  bool diag_cotangent(const Call& c, const qdc_plan_op& op) const {
     if (op.type != QDC_PLAN_OP || !is_diff_density(ins[op.instr].kind)) return false;
     const int R = is_q1_density(ins[op.instr].kind) ? 2 : 4;
     if (op.pos2 >= (uint32_t)(4 * DI_GROUPS) || op.pos1 >= (uint32_t)(4 * DI_GROUPS)) return false;
     if (R == 4 && op.pos2 / 4 != op.pos1 / 4) return false;  // both bits in one table group
-    const qdc_complex* g = dg.at(gidx[op.instr]);
+    const qdc_complex* g = c.dg->at(c.gidx[op.instr]);
     for (int p = 0; p < R; ++p)
       for (int q = 0; q < R; ++q)
         if (p != q && (g[p * R + q].re != 0 || g[p * R + q].im != 0)) return false;
     return true;
   }
-  // Consecutive items that are injections only, all with diagonal cotangents, become one item of
-  // type 3 (their plan ops in order).  Injections only add to bwd from the (unchanged) fwd, so a
+  // Consecutive items that are injections only, all with diagonal cotangents, become one
+  // ITEM_DIAG_INJECT (their plan ops in order).  Injections only add to bwd from the (unchanged) fwd, so a
   // run of them commutes and sums.
-  void merge_diag_injections(std::vector<Item>& items, const std::vector<qdc_plan_op>& pl,
-                             const Flat& dg, const std::vector<size_t>& gidx) const {
+  void merge_diag_injections(Call& c) const {
     auto eligible = [&](const Item& it) {
-      if (it.type != 0 && it.type != 2) return false;
+      if (it.type != ITEM_OP && it.type != ITEM_FUSED) return false;
       for (uint32_t k : it.ops)
-        if (!diag_cotangent(pl[k], dg, gidx)) return false;
+        if (!diag_cotangent(c, c.plan[k])) return false;
       return !it.ops.empty();
     };
     std::vector<Item> out;
-    for (Item& it : items) {
+    for (Item& it : c.items) {
       if (eligible(it)) {
-        if (!out.empty() && out.back().type == 3) {
+        if (!out.empty() && out.back().type == ITEM_DIAG_INJECT) {
           out.back().ops.insert(out.back().ops.end(), it.ops.begin(), it.ops.end());
           continue;
         }
         Item m;
-        m.type = 3;
+        m.type = ITEM_DIAG_INJECT;
         m.ops = it.ops;
         out.push_back(std::move(m));
         continue;
       }
       out.push_back(std::move(it));
     }
-    items = std::move(out);
+    c.items = std::move(out);
   }
-  // D(i) tables of a type-3 item: T[g * 16 + e] = sum of the diagonal entries that the densities
+  // D(i) tables of an ITEM_DIAG_INJECT: T[g * 16 + e] = sum of the diagonal entries that the densities
   // on bits 4g..4g+3 select for the pattern e of those bits (summed in double); returns the
   // number of groups in use
-  uint32_t diag_table(const Item& item, const std::vector<qdc_plan_op>& pl, const Flat& dg,
-                      const std::vector<size_t>& gidx, diag_tab& T) const {
+  uint32_t diag_table(const Call& c, const Item& item, diag_tab& T) const {
     cd acc[DI_GROUPS * 16] = {};
     uint32_t ng = 1;
     for (uint32_t k : item.ops) {
-      const qdc_plan_op& op = pl[k];
+      const qdc_plan_op& op = c.plan[k];
       const bool q1 = is_q1_density(ins[op.instr].kind);
       const int R = q1 ? 2 : 4;
-      const qdc_complex* gd = dg.at(gidx[op.instr]);
+      const qdc_complex* gd = c.dg->at(c.gidx[op.instr]);
       const uint32_t grp = op.pos2 / 4;
       ng = std::max(ng, grp + 1);
       for (uint32_t e = 0; e < 16; ++e) {
@@ -2007,56 +2008,30 @@ struct Circuit {
     return reverse_dense<4>(ctx, f, b, GateMats::dense<4>(M.a), GateMats::dense<4>(M.b), p2, p1, nl,
                             gbase, dst);
   }
-  // one plan op of the reverse sweep outside the fused passes, on every shard: a gate (before the
-  // first cotangent it only uncomputes fwd), or a density's cotangent injection
-  const char* backward_op(const qdc_plan_op& op, const Flat& dg, const Flat& cg, const Flat& vg,
-                          const std::vector<size_t>& gidx, const std::vector<uint32_t>& var_idx,
-                          bool& have_bwd) {
-    const Instr& in = ins[op.instr];
-    const bool gate = is_const(in.kind) || is_var(in.kind), var = is_var(in.kind);
-    const qdc_complex* g4 = (!gate ? dg : var ? vg : cg).at(gidx[op.instr]);
-    for (auto& s : sh) {
-      Ctx& ctx = s.c();
-      QDC_TRY(ctx.use());
-      if (gate && !have_bwd)
-        QDC_TRY(apply_gate(ctx, in, g4, s.state, op.pos2, op.pos1, true));
-      else if (gate)
-        QDC_TRY(reverse_gate(ctx, in, g4, s.state, s.bwd, op.pos2, op.pos1, var ? s.grads : nullptr,
-                             var_idx[op.instr]));
-      else if (is_q1_density(in.kind))
-        QDC_TRY(inject<2>(ctx, s.state, s.bwd, transpose<2>(to_mat<2>(g4)), op.pos2, op.pos2, nl,
-                          !have_bwd));
-      else
-        QDC_TRY(inject<4>(ctx, s.state, s.bwd, transpose<4>(to_mat<4>(g4)), op.pos2, op.pos1, nl,
-                          !have_bwd));
-    }
-    if (!gate) have_bwd = true;
-    return nullptr;
-  }
   // The backward's schedule: the forward's passes in reverse (mirror_schedule) when this backward
   // follows that forward with the same gates, else its own plan, fused as usual
-  const char* schedule_backward(const Flat& cg, const Flat& vg, std::vector<qdc_plan_op>& pl,
-                                std::vector<Item>& items, size_t& first_inject) {
+  const char* schedule_backward(Call& c) {
     bool mirrored = false;
     if (mirror_on() && mrec.valid && mrec.inexact == inexact && mrec.end_phys == layout.phys)
-      mirrored = mrec.same_gates(cg, vg) && mirror_schedule(pl, items, first_inject);
+      mirrored = mrec.same_gates(*c.cg, *c.vg) && mirror_schedule(c);
     mrec.valid = false;  // (this backward changes the layout and the state)
     if (mirrored) return nullptr;
-    pl = plan(QDC_PLAN_BACKWARD);
-    first_inject = first_injection(pl);
+    c.plan = plan(QDC_PLAN_BACKWARD);
+    c.first_inject = first_injection(c.plan);
     // QDC_MIRROR=2 (tests): a backward that cannot mirror its forward is an error
     if (mirror_on() && k.mirror == 2)
       return fail("mirror: the backward does not follow a forward call with the same gates");
-    items = schedule(pl, true, first_inject);
+    schedule(c);
     return nullptr;
   }
   const char* backward(const Flat& dg, const Flat& cg, const Flat& vg, qdc_complex* out) {
-    hclock::time_point ht[6];
-    ht[0] = hclock::now();
-    std::vector<size_t> gidx;
-    QDC_TRY(validate_backward(dg, cg, vg, gidx));
+    Call c(*this, QDC_PLAN_BACKWARD, true, false, &cg, &vg, &dg);
+    QDC_TRY(validate_backward(dg, cg, vg, c.gidx));
     if (!dry) QDC_TRY(dyn_reset_all());
-    const size_t nvar = n_var();
+    c.var_idx.assign(ins.size(), 0);
+    for (size_t k = 0; k < ins.size(); ++k)
+      if (is_var(ins[k].kind)) c.var_idx[k] = c.nvar++;
+    const size_t nvar = c.nvar;
     for (auto& s : sh) {
       if (!s.bwd) {
         QDC_TRY(s.c().use());
@@ -2073,75 +2048,24 @@ struct Circuit {
       QDC_TRY(s.c().use());
       QDC_HIP(hipMemsetAsync(s.grads, 0, sizeof(cx) * nslots * RED, s.c().stream));
     }
-    std::vector<uint32_t> var_idx(ins.size(), 0);
-    {
-      uint32_t v = 0;
-      for (size_t k = 0; k < ins.size(); ++k)
-        if (is_var(ins[k].kind)) var_idx[k] = v++;
-    }
-    bool have_bwd = false;
-    mark_inexact(cg, vg, gidx);
-    ht[1] = hclock::now();
-    std::vector<qdc_plan_op> pl;
-    std::vector<Item> items;
-    size_t first_inject = 0;
-    QDC_TRY(schedule_backward(cg, vg, pl, items, first_inject));
-    if (k.diag_inject) merge_diag_injections(items, pl, dg, gidx);
-    ht[2] = hclock::now();
-    // a run of diagonal cotangent injections: one elementwise pass (no pass program)
-    auto run_diag_inject = [&](const Item& item) -> const char* {
-      diag_tab T;
-      const uint32_t ng = diag_table(item, pl, dg, gidx, T);
-      for (auto& s : sh) {
-        QDC_TRY(s.c().use());
-        QDC_TRY(qdc::diag_inject(s.c(), s.state, s.bwd, T, ng, nl, gm, have_bwd));
-      }
-      have_bwd = true;
-      return nullptr;
-    };
+    mark_inexact(cg, vg, c.gidx);
+    c.ht[1] = hclock::now();
+    QDC_TRY(schedule_backward(c));
+    if (k.diag_inject) merge_diag_injections(c);
+    c.ht[2] = hclock::now();
     // the backward's leading diagonal-injection passes need no program: they are launched
     // before it is built, so the device runs them during the host's build (round 6;
     // QDC_EARLY_INJECT=0: after)
     size_t lead = 0;
     if (!dry && k.early_inject)
-      for (; lead < items.size() && items[lead].type == 3; ++lead) QDC_TRY(run_diag_inject(items[lead]));
-    size_t mats_off = 0;
-    const auto tb0 = std::chrono::steady_clock::now();
-    QDC_TRY(build_program(items, pl, true, first_inject, cg, vg, gidx, mats_off, var_idx,
-                          (uint32_t)nvar, {}, &dg));
-    ht[3] = hclock::now();
-    if (dry) return tracing ? trace_logical(items, pl, true, cg, vg, gidx) : nullptr;
-    if (k.rq_stats)
-      fprintf(stderr, "backward plan+build %.3f ms\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tb0).count());
-    for (size_t ii = lead; ii < items.size(); ++ii) {
-      const Item& item = items[ii];
-      if (item.type == 3) {
-        QDC_TRY(run_diag_inject(item));
-        continue;
-      }
-      if (item.type == 2) {
-        const bool two = item.ops[0] >= first_inject;
-        if (two && !have_bwd) {  // the first injection is fused: it adds into a zero bwd
-          for (auto& s : sh) {
-            QDC_TRY(s.c().use());
-            QDC_TRY(zero_bwd(s));
-          }
-          have_bwd = true;
-        }
-        QDC_TRY(run_fused(item, two, mats_off, true));
-        continue;
-      }
-      const qdc_plan_op& op = pl[item.ops[0]];
-      if (op.type == QDC_PLAN_REMAP) {
-        QDC_TRY(item.inv ? unremap(op, have_bwd) : remap(op, have_bwd));
-        continue;
-      }
-      QDC_TRY(backward_op(op, dg, cg, vg, gidx, var_idx, have_bwd));
-    }
-    ht[4] = hclock::now();
+      for (; lead < c.items.size() && c.items[lead].type == ITEM_DIAG_INJECT; ++lead)
+        QDC_TRY(run_diag_inject(c, c.items[lead]));
+    QDC_TRY(build_and_trace(c, "backward"));
+    QDC_TRY(run_items(c, lead));
+    if (dry) return nullptr;
+    c.ht[4] = hclock::now();
     QDC_TRY(flush_all());
-    const size_t used = nvar + stage_post.size();
+    const size_t used = nvar + c.stage_post.size();
     std::vector<cx*> bufs;
     for (auto& s : sh) bufs.push_back(s.grads);
     QDC_TRY(ex.allreduce(sh, bufs, used * RED));
@@ -2150,13 +2074,13 @@ struct Circuit {
       if (is_var(in.kind)) widths.push_back(gate_len(in.kind));
     QDC_TRY(collect(sh[0].grads, widths, out, used));
     // gradients of fused stages: G = ptrace(L Gamma Rt) per gate (qdc_stage.hpp)
-    if (!stage_post.empty()) {
+    if (!c.stage_post.empty()) {
       std::vector<size_t> off(widths.size() + 1, 0);
       for (size_t j = 0; j < widths.size(); ++j) off[j + 1] = off[j] + widths[j];
-      stage_gradients(stage_post, host_out, (size_t)RED, off, widths, out);
+      stage_gradients(c.stage_post, host_out, (size_t)RED, off, widths, out);
     }
-    ht[5] = hclock::now();
-    host_record(1, ht);
+    c.ht[5] = hclock::now();
+    host_record(1, c.ht);
     return nullptr;
   }
 };

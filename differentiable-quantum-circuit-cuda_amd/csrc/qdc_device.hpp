@@ -66,6 +66,10 @@ struct ProfRecord {
   hipEvent_t a, b;
 };
 
+struct ProfSpan {
+  hipEvent_t a = nullptr, b = nullptr;
+};
+
 struct Prof {
   bool on = false;
   std::vector<hipEvent_t> pool;
@@ -370,6 +374,24 @@ struct Ctx {
     stream = nullptr;
   }
 
+  // The profiling bracket of one launch (or one exchange) on this context's stream: a pair of
+  // events from the pool, the first recorded before the work, the second after it with the
+  // launch's record.  Nothing when profiling is off or the pool gave no event.
+  ProfSpan prof_begin() {
+    ProfSpan p;
+    if (prof.on) {
+      p.a = prof.get();
+      p.b = prof.get();
+      if (p.a) (void)hipEventRecord(p.a, stream);
+    }
+    return p;
+  }
+  void prof_end(const ProfSpan& p, const char* name, double bytes, double flops) {
+    if (prof.on && p.a && p.b) {
+      (void)hipEventRecord(p.b, stream);
+      prof.recs.push_back({name, bytes, flops, p.a, p.b});
+    }
+  }
 
   template <typename K, typename... Args>
   const char* launch(const char* name, double bytes, K kernel, uint32_t grid, Args... args) {
@@ -378,20 +400,12 @@ struct Ctx {
   template <typename K, typename... Args>
   const char* launch_block(const char* name, double bytes, K kernel, uint32_t grid,
                            uint32_t block, Args... args) {
-    hipEvent_t a = nullptr, b = nullptr;
-    if (prof.on) {
-      a = prof.get();
-      b = prof.get();
-      if (a) (void)hipEventRecord(a, stream);
-    }
+    const ProfSpan span = prof_begin();
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, stream, args...);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
       return fail("HIP ERROR: launch of kernel %s failed with %s.", name, hipGetErrorName(e));
-    if (prof.on && a && b) {
-      (void)hipEventRecord(b, stream);
-      prof.recs.push_back({name, bytes, next_flops, a, b});
-    }
+    prof_end(span, name, bytes, next_flops);
     next_flops = 0;
     return nullptr;
   }
@@ -406,12 +420,7 @@ struct Ctx {
   template <typename... Args>
   const char* launch_module(const char* name, double bytes, hipFunction_t fn, uint32_t grid,
                             uint32_t block, Args... args) {
-    hipEvent_t a = nullptr, b = nullptr;
-    if (prof.on) {
-      a = prof.get();
-      b = prof.get();
-      if (a) (void)hipEventRecord(a, stream);
-    }
+    const ProfSpan span = prof_begin();
     void* params[] = {(void*)&args...};
     hipError_t e = hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, 0, stream, params, nullptr);
     if (e == hipSuccess) e = hipGetLastError();
@@ -419,10 +428,7 @@ struct Ctx {
       return fail("HIP ERROR: launch of kernel %s (specialized) failed with %s.", name,
                   hipGetErrorName(e));
     spec_launches().fetch_add(1, std::memory_order_relaxed);
-    if (prof.on && a && b) {
-      (void)hipEventRecord(b, stream);
-      prof.recs.push_back({name, bytes, next_flops, a, b});
-    }
+    prof_end(span, name, bytes, next_flops);
     next_flops = 0;
     return nullptr;
   }

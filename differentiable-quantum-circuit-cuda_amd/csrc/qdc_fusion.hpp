@@ -52,11 +52,18 @@ inline bool is_diff_density(int k) {
 inline bool is_q1_density(int k) { return k == QDC_Q1_DENSITY || k == QDC_DIFF_Q1_DENSITY; }
 inline int gate_len(int k) { return is_q2_dense(k) ? 16 : 4; }
 
-// One unit of work of a pass program: a single plan op (type 0), a remap (1) or a fused pass
-// (2) with its tile: lc contiguous chunk bits + h row bits hb[].
+// What an item of a call's schedule is (FusionItem::type; qdc_fusion_schedule exports the values)
+enum ItemType : int {
+  ITEM_OP = 0,           // one plan op on its own kernel
+  ITEM_REMAP = 1,        // a remap of the shards' qubits
+  ITEM_FUSED = 2,        // a fused pass
+  ITEM_DIAG_INJECT = 3,  // a run of diagonal cotangent injections (qdc_circuit.hpp)
+};
+// One unit of work of a pass program: a single plan op, a remap or a fused pass with its tile:
+// lc contiguous chunk bits + h row bits hb[].
 struct FusionItem {
-  int type;
-  std::vector<uint32_t> ops;  // plan indices, in execution order for type 2 passes
+  int type;  // ItemType
+  std::vector<uint32_t> ops;  // plan indices, in execution order for ITEM_FUSED passes
   uint32_t lc = 0, h = 0, hb[FMAX_ROWS] = {};
   // physical qubit swaps the pass applies on its way out (its store writes the permuted
   // layout; later ops' positions are already rewritten), in order
@@ -316,12 +323,12 @@ struct FusionPlanner {
     while (i < plan.size()) {
       const qdc_plan_op& op = plan[i];
       if (op.type == QDC_PLAN_REMAP) {
-        items.push_back(FusionItem{1, {(uint32_t)i}});
+        items.push_back(FusionItem{ITEM_REMAP, {(uint32_t)i}});
         ++i;
         continue;
       }
       if (!on || !fusable(i)) {
-        items.push_back(FusionItem{0, {(uint32_t)i}});
+        items.push_back(FusionItem{ITEM_OP, {(uint32_t)i}});
         ++i;
         continue;
       }
@@ -341,9 +348,9 @@ struct FusionPlanner {
         ScannedPass sp = search ? search_pass(plan, rem, rules)
                                 : scan_pass(plan, rem.data(), rem.size(), rules, ~0ull, false);
         if (sp.ops.size() == 1) {
-          items.push_back(FusionItem{0, sp.ops});
+          items.push_back(FusionItem{ITEM_OP, sp.ops});
         } else {
-          FusionItem it{2, sp.ops};
+          FusionItem it{ITEM_FUSED, sp.ops};
           tile_config(sp.mask, T, it.lc, it.h, it.hb);
           bool gates_only = it.lc >= NLOW - LV;  // the low positions are tile bits
           for (uint32_t k : sp.ops) gates_only = gates_only && is_gate_op(plan[k]);

@@ -117,3 +117,27 @@ __device__ __forceinline__ void spec_xchg_imm(cx (&x)[R], const SpecEnv& E, cons
 }
 
 }  // namespace qdc
+
+#ifndef QDC_SPEC_TU  // (host side: not in the specialized kernels' translation units)
+#include "qdc_jit.hpp"
+
+namespace qdc {
+
+// A program whose relayouts all keep a slot runs on half buffers where its variant has that
+// form (spec_half: QDC_SPEC_HALF; never with the immediate-offset relayouts)
+inline bool spec_half_buffer(const RqVariant& V, bool spec_half, const std::vector<SpecStep>& steps) {
+  return V.pass_half && spec_half && !spec_imm() && spec_half_ok(steps);
+}
+// The specialized kernel (name, source) of the pass program `steps` on variant V
+inline SpecEntry spec_kernel_of(const std::vector<SpecStep>& steps, const RqVariant& V,
+                                uint32_t tbits, bool half) {
+  const SpecKind K = spec_kind(V, half);
+  const std::string body = spec_program_source(steps, tbits, K);
+  SpecEntry e;
+  e.name = spec_kernel_name(body, K);
+  e.src = spec_kernel_source(e.name, body, K);
+  return e;
+}
+
+}  // namespace qdc
+#endif  // QDC_SPEC_TU

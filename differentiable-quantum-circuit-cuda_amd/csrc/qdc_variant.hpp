@@ -135,4 +135,18 @@ inline const RqVariant* rq_select(bool two, uint32_t tbits, const RqKnobs& k, bo
   return nullptr;
 }
 
+// A variant's five-slot passes (2^11 tiles) are planned to keep a slot in place across every
+// relayout where they can, for the half-buffer specialized form (rq_plan keep; spec_half:
+// QDC_SPEC_HALF)
+inline bool rq_keep(const RqVariant& V, bool spec_half) { return spec_half && V.ns == 5; }
+
+// The slot case a stage of this kind runs with, from the plan's case cs = 8 S1 + S2: two-qubit
+// and diagonal stages run with the lower slot first (half the kernels' cases).  swapped: the
+// slots were exchanged, so the caller exchanges the matrices' index bits to match.
+inline uint32_t rq_slot_case(uint32_t kind, uint32_t cs, bool& swapped) {
+  const uint32_t kd = kind & 7u;
+  swapped = (kd == FK_Q2 || kd == FK_DIAG) && (cs >> 3) > (cs & 7u);
+  return swapped ? (cs & 7u) * 8u + (cs >> 3) : cs;
+}
+
 }  // namespace qdc

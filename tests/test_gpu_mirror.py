@@ -80,7 +80,7 @@ def c5_floors():
 def test_c5_depth_10k_gates_sharded(strict_mirror, c5_floors, prec, kw):
     """Config C5's depth on the sharded path (the path the 8-GPU config runs): the forward's
     remap plan keeps both directions' order relations and the backward undoes every remap in
-    reverse (qdc_circuit.hpp unremap), so each reverse pass uncomputes with the adjoint of the
+    reverse (qdc_circuit.hpp remap, inverse), so each reverse pass uncomputes with the adjoint of the
     forward's stage matrix in the layout the forward applied it.  QDC_MIRROR=2: a sharded
     backward that did not mirror its forward is an error.  Every output within 4x the floor of
     the reference's own gate-by-gate algorithm (src/circuit.rs:280-392)."""

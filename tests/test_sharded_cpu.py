@@ -72,7 +72,8 @@ def unpack(shard, victims, nl):
 
 
 def unremap(shard, r, nl, world):
-    """The runtime's unremap (csrc/qdc_circuit.hpp): the all-to-all, then the inverse pack."""
+    """The runtime's inverse remap (csrc/qdc_circuit.hpp remap(op, inverse)): the all-to-all, then
+    the inverse pack."""
     t = torch.from_numpy(np.ascontiguousarray(shard)).view(torch.float64)
     out = torch.empty_like(t)
     dist.all_to_all_single(out, t)
