@@ -17,6 +17,7 @@
 #include "qdc_qkgrad.hpp"
 #include "qdc_pauli.hpp"
 #include "qdc_paulirot.hpp"
+#include "qdc_paulilayer.hpp"
 
 namespace qdc {
 
@@ -440,6 +441,43 @@ __attribute__((visibility("default"))) size_t qdc_pauli_plan(
   for (uint64_t x : plan.win_x) group_x[w++] = x;
   for (uint64_t x : plan.far_x) group_x[w++] = x;
   return ng;
+}
+
+// ---- diagonal Pauli layers exp(-i/2 sum_k theta_k Z^{z_k}) (qdc_paulilayer.hpp) ---------------
+
+__attribute__((visibility("default"))) const char* qdc_pauli_layer(
+    qdc_complex* state, const unsigned long long* zmask, const double* theta, size_t terms,
+    size_t n) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  QDC_TRY(qdc::pl_check(zmask, theta, terms, n));
+  if (!theta) return qdc::fail("The layer has no angles.");
+  return qdc::pauli_layer(ctx, reinterpret_cast<qdc::cx*>(state), zmask, theta, terms,
+                          (uint32_t)n);
+}
+
+__attribute__((visibility("default"))) const char* qdc_pauli_layer_reverse(
+    qdc_complex* fwd, qdc_complex* bwd, const unsigned long long* zmask, const double* theta,
+    size_t terms, size_t n, double* dtheta) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  QDC_TRY(qdc::pl_check(zmask, theta, terms, n));
+  if (!theta) return qdc::fail("The layer has no angles.");
+  if (fwd == bwd) return qdc::fail("fwd and bwd must be different states.");
+  if (!bwd && dtheta) return qdc::fail("A gradient needs a bwd state.");
+  return qdc::pauli_layer_reverse(ctx, reinterpret_cast<qdc::cx*>(fwd),
+                                  reinterpret_cast<qdc::cx*>(bwd), zmask, theta, terms,
+                                  (uint32_t)n, dtheta);
+}
+
+// host only: no context, no device
+__attribute__((visibility("default"))) size_t qdc_pauli_layer_plan(
+    const unsigned long long* zmask, size_t terms, size_t n, unsigned* out) {
+  if (!out || n > 40 || qdc::pl_check(zmask, nullptr, terms, n)) return SIZE_MAX;
+  const qdc::PauliLayerPlan P = qdc::pl_plan(zmask, terms);
+  const unsigned v[6] = {qdc::PL_L, P.groups, P.high, P.fwd, P.rev, P.rev_grad};
+  for (int i = 0; i < 6; ++i) out[i] = v[i];
+  return P.groups;
 }
 
 __attribute__((visibility("default"))) const char* qdc_abi_sync(void) {

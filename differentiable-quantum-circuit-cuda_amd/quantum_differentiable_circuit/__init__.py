@@ -23,11 +23,11 @@ import numpy as np
 from .common_gates import get_cnot, get_hadamard  # noqa: E402  (common_gates.rs)
 from ._native import (PanicException, KernelStat, PlanOp, check, default_precision, load,
                       ptr, PRECISIONS)
-from .observable import PauliSum, pauli_masks
+from .observable import PauliSum, layer_angles, layer_masks, pauli_layer_plan, pauli_masks
 
 __all__ = ["Circuit", "Circuit32", "Circuit64", "QuantizedTensor", "PanicException",
            "get_q1_grad", "get_q2_grad", "get_q2_grad_diag", "get_qk_grad", "data_transfer",
-           "PauliSum", "pauli_inject", "pauli_rot_reverse",
+           "PauliSum", "pauli_inject", "pauli_rot_reverse", "pauli_layer_reverse", "pauli_layer_plan",
            "circuit_class",
            "plan", "unpermute", "get_hadamard", "get_cnot"]
 
@@ -768,6 +768,16 @@ class QuantizedTensor:
         x, z = pauli_masks(self.qubits_number, ops)
         check(self._lib.qdc_pauli_rot(self._p, x, z, _real_angle(theta), self.qubits_number))
 
+    def apply_pauli_layer(self, strings, thetas):
+        """state <- exp(-i/2 sum_k thetas[k] P_k) state for Z-only strings P_k (each in the forms
+        of ``apply_pauli_rotation``; qdc_pauli_layer, include/qdc/pauli.h): the product of the K
+        rotations in one pass over the state per 128 strings."""
+        z = layer_masks(self.qubits_number, strings)
+        t = layer_angles(thetas, z.size)
+        check(self._lib.qdc_pauli_layer(self._p, z.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                        t.ctypes.data_as(C.POINTER(C.c_double)), z.size,
+                                        self.qubits_number))
+
     def apply_q2_gate_inv(self, gate, pos2, pos1):
         g = self._gate(gate, 16)
         self._pos2(pos2, pos1)
@@ -879,3 +889,25 @@ def pauli_rot_reverse(fwd, bwd, ops, theta, want_grad=True) -> float:
     check(fwd._lib.qdc_pauli_rot_reverse(fwd._p, bwd._p, x, z, t, fwd.qubits_number,
                                          C.byref(d) if want_grad else None))
     return float(d.value)
+
+
+def pauli_layer_reverse(fwd, bwd, strings, thetas, want_grad=True) -> np.ndarray:
+    """One reverse step of ``fwd.apply_pauli_layer(strings, thetas)`` (qdc_pauli_layer_reverse),
+    in one pass over both states per 32 strings (128 without gradients): fwd <- e^{+i phi} fwd,
+    bwd <- e^{-i phi} bwd, and dL/dtheta_k = 1/2 Im sum_i s_k(i) bwd[i] fwd[i] as a float64 array
+    of K values; zeros when ``want_grad`` is false (a constant layer) or ``bwd`` is None (no
+    cotangent yet: only the uncompute)."""
+    z = layer_masks(fwd.qubits_number, strings)
+    t = layer_angles(thetas, z.size)
+    zp = z.ctypes.data_as(C.POINTER(C.c_ulonglong))
+    tp = t.ctypes.data_as(C.POINTER(C.c_double))
+    d = np.zeros(z.size, np.float64)
+    if bwd is None:
+        check(fwd._lib.qdc_pauli_layer_reverse(fwd._p, None, zp, tp, z.size, fwd.qubits_number,
+                                               None))
+        return d
+    if fwd.qubits_number != bwd.qubits_number:
+        raise PanicException("fwd and bwd have different lengths.")
+    dp = d.ctypes.data_as(C.POINTER(C.c_double)) if want_grad else None
+    check(fwd._lib.qdc_pauli_layer_reverse(fwd._p, bwd._p, zp, tp, z.size, fwd.qubits_number, dp))
+    return d

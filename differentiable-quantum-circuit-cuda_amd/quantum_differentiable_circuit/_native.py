@@ -41,6 +41,7 @@ RUNTIME = (
     "qdc_knob_table",
     "qdc_pauli_energy", "qdc_pauli_inject", "qdc_pauli_plan",
     "qdc_pauli_rot", "qdc_pauli_rot_reverse",
+    "qdc_pauli_layer", "qdc_pauli_layer_reverse", "qdc_pauli_layer_plan",
 )
 
 
@@ -132,6 +133,10 @@ def _proto(lib):
         "qdc_pauli_rot": (_E, [_P, C.c_ulonglong, C.c_ulonglong, C.c_double, _S]),
         "qdc_pauli_rot_reverse": (_E, [_P, _P, C.c_ulonglong, C.c_ulonglong, C.c_double, _S,
                                        C.POINTER(C.c_double)]),
+        "qdc_pauli_layer": (_E, [_P, C.POINTER(C.c_ulonglong), C.POINTER(C.c_double), _S, _S]),
+        "qdc_pauli_layer_reverse": (_E, [_P, _P, C.POINTER(C.c_ulonglong),
+                                         C.POINTER(C.c_double), _S, _S, C.POINTER(C.c_double)]),
+        "qdc_pauli_layer_plan": (_S, [C.POINTER(C.c_ulonglong), _S, _S, C.POINTER(C.c_uint)]),
         "qdc_abi_sync": (_E, []),
         "qdc_abi_profile": (_E, [C.c_int]),
         "qdc_abi_profile_collect": (_S, [C.POINTER(KernelStat), _S]),

@@ -23,6 +23,14 @@ takes its angle, a real scalar, from the same FIFO as the gates of its class: fo
 before the first cotangent), and a variable rotation's gradient is dL/dtheta, a Python float at
 its place among the variable gates' gradients (0.0 before the first cotangent).
 
+A diagonal Pauli layer ``exp(-i/2 sum_k theta_k P_k)`` of Z-only strings
+(``add_const_pauli_layer`` / ``add_var_pauli_layer``) takes one FIFO entry of its class, the real
+array of its K angles: forward is one ``apply_pauli_layer``, backward one ``pauli_layer_reverse``,
+and a variable layer's gradient is a float64 array of K (zeros before the first cotangent).
+``add_const_pauli_evolution(H)`` / ``add_var_pauli_evolution(H)`` is the same layer with one real
+scalar theta for a ``PauliSum`` H of Z strings, ``U = exp(-i theta/2 H)`` (theta_k = theta c_k,
+the QAOA cost layer); its gradient is the float ``sum_k c_k dtheta_k``.
+
 Gates are 1-D arrays of 4^k values (2^k x 2^k row-major, local index bit (k-1-b) = qubit
 positions[b]); densities come back as (2^k, 2^k) arrays and gradients as 1-D arrays in forward
 order.  At k = 1, 2 every call lands on the q1 / q2 kernels, so a circuit of 1- and 2-qubit
@@ -41,11 +49,14 @@ from typing import List
 import numpy as np
 
 from . import (PanicException, PauliSum, QuantizedTensor, _real_angle, data_transfer,
-               get_qk_grad, pauli_inject, pauli_masks, pauli_rot_reverse)
+               get_qk_grad, layer_angles, layer_masks, pauli_inject, pauli_layer_reverse,
+               pauli_masks, pauli_rot_reverse)
 from .abi_circuit import _slice
 
 (CONST_GATE, VAR_GATE, DENSITY, DIFF_DENSITY, OBSERVABLE, DIFF_OBSERVABLE, CONST_ROT,
- VAR_ROT) = range(8)
+ VAR_ROT, CONST_LAYER, VAR_LAYER, CONST_EVOL, VAR_EVOL) = range(12)
+_CONST_KINDS = (CONST_GATE, CONST_ROT, CONST_LAYER, CONST_EVOL)
+
 
 
 class DenseCircuit:
@@ -95,6 +106,38 @@ class DenseCircuit:
     def add_const_pauli_rotation(self, ops): self._push_rotation(CONST_ROT, ops)
     def add_var_pauli_rotation(self, ops): self._push_rotation(VAR_ROT, ops)
 
+    def _push_layer(self, kind, strings):
+        strings = tuple(s if isinstance(s, str) else tuple(s) for s in strings)
+        if not strings:
+            raise PanicException("The layer has no terms.")
+        # (the parser's panics when the circuit is built; the masks are kept, not the strings)
+        self.instructions.append((kind, (layer_masks(self.state.qubits_number, strings), None)))
+
+    def add_const_pauli_layer(self, strings): self._push_layer(CONST_LAYER, strings)
+    def add_var_pauli_layer(self, strings): self._push_layer(VAR_LAYER, strings)
+
+    def _push_evolution(self, kind, h):
+        if not isinstance(h, PauliSum):
+            raise TypeError("argument 'H': expected a PauliSum")
+        if h.qubits_number != self.state.qubits_number:
+            raise PanicException("The observable and the tensor have different sizes.")
+        if len(h) == 0:
+            raise PanicException("The layer has no terms.")
+        if np.any(h.xmasks != 0):
+            raise PanicException("a Pauli layer takes Z strings only.")
+        self.instructions.append((kind, (h.zmasks.copy(), h.coeffs.copy())))
+
+    def add_const_pauli_evolution(self, h): self._push_evolution(CONST_EVOL, h)
+    def add_var_pauli_evolution(self, h): self._push_evolution(VAR_EVOL, h)
+
+    @staticmethod
+    def _layer_angles(kind, pos, entry):
+        """The K angles of a layer instruction from its FIFO entry."""
+        zmasks, coeffs = pos
+        if kind in (CONST_EVOL, VAR_EVOL):
+            return _real_angle(entry) * coeffs
+        return layer_angles(entry, zmasks.size)
+
     # --- forward --------------------------------------------------------------------------
     def _forward(self, const_gates, var_gates, all_densities) -> List[np.ndarray]:
         if not self.instructions:
@@ -116,6 +159,12 @@ class DenseCircuit:
                     word = "constant" if kind == CONST_ROT else "variable"
                     raise PanicException(f"The number of {word} gates is less than required.")
                 s.apply_pauli_rotation(pos, _real_angle(pool.popleft()))
+            elif kind in (CONST_LAYER, VAR_LAYER, CONST_EVOL, VAR_EVOL):
+                pool = cg if kind in _CONST_KINDS else vg
+                if not pool:
+                    word = "constant" if kind in _CONST_KINDS else "variable"
+                    raise PanicException(f"The number of {word} gates is less than required.")
+                s.apply_pauli_layer(pos[0], self._layer_angles(kind, pos, pool.popleft()))
             elif kind in (OBSERVABLE, DIFF_OBSERVABLE):
                 if kind == DIFF_OBSERVABLE or all_densities:
                     out.append(s.pauli_energy(pos))
@@ -169,6 +218,16 @@ class DenseCircuit:
                                       want_grad=kind == VAR_ROT)
                 if kind == VAR_ROT:
                     grads.appendleft(d)
+            elif kind in (CONST_LAYER, VAR_LAYER, CONST_EVOL, VAR_EVOL):
+                pool = cg if kind in _CONST_KINDS else vg
+                if not pool:
+                    raise PanicException("The number of gates is less than required.")
+                d = pauli_layer_reverse(fwd, bwd, pos[0], self._layer_angles(kind, pos, pool.pop()),
+                                        want_grad=kind in (VAR_LAYER, VAR_EVOL))
+                if kind == VAR_LAYER:
+                    grads.appendleft(d)
+                elif kind == VAR_EVOL:
+                    grads.appendleft(float(np.dot(pos[1], d)))
             elif kind == DIFF_DENSITY:
                 if not dens:
                     raise PanicException(

@@ -185,3 +185,52 @@ def plan_masks(qubits_number, xmasks, zmasks, precision=None):
     return {"W": out[0], "merged": out[1], "window_groups": out[2], "far_groups": out[3],
             "energy_launches": out[4], "inject_launches": out[5],
             "group_x": [int(gx[i]) for i in range(k)]}
+
+
+def layer_masks(qubits_number: int, strings):
+    """The zmasks (uint64 array) of a diagonal Pauli layer: ``strings`` is a sequence of Pauli
+    strings in the forms ``pauli_masks`` accepts, Z letters only; a uint64 array is taken as the
+    masks themselves (the library checks their range)."""
+    if isinstance(strings, np.ndarray) and strings.dtype == np.uint64 and strings.ndim == 1:
+        return np.ascontiguousarray(strings)
+    if isinstance(strings, str):
+        raise PanicException("a Pauli layer takes a sequence of strings.")
+    zs = []
+    for ops in strings:
+        x, z = pauli_masks(qubits_number, ops)
+        if x:
+            raise PanicException("a Pauli layer takes Z strings only.")
+        zs.append(z)
+    return np.array(zs, dtype=np.uint64)
+
+
+def layer_angles(thetas, count):
+    """The angles of a layer of ``count`` strings: a real 1-D float64 array of that length."""
+    t = np.asarray(thetas)
+    if t.ndim != 1 or t.size != count:
+        raise PanicException("a Pauli layer takes one angle per string.")
+    if np.iscomplexobj(t):
+        if np.any(t.imag != 0.0):
+            raise PanicException("A rotation angle must be real.")
+        t = t.real
+    return np.ascontiguousarray(t, dtype=np.float64)
+
+
+def pauli_layer_plan(qubits_number, strings, precision=None):
+    """The launch plan of a diagonal Pauli layer (qdc_pauli_layer_plan, host only): ``{"L",
+    "groups", "high_terms", "forward_launches", "reverse_launches", "reverse_grad_launches"}``;
+    ``strings`` as for ``apply_pauli_layer``, or an integer array of zmasks.  None where the
+    library rejects the masks."""
+    from ._native import default_precision, load
+    lib = load(precision or default_precision())
+    if isinstance(strings, np.ndarray) and strings.dtype.kind in "iu":
+        zs = np.ascontiguousarray(strings, dtype=np.uint64)
+    else:
+        zs = layer_masks(qubits_number, strings)
+    out = (C.c_uint * 6)()
+    k = lib.qdc_pauli_layer_plan(zs.ctypes.data_as(C.POINTER(C.c_ulonglong)), zs.size,
+                                 int(qubits_number), out)
+    if k == C.c_size_t(-1).value:
+        return None
+    return {"L": out[0], "groups": out[1], "high_terms": out[2], "forward_launches": out[3],
+            "reverse_launches": out[4], "reverse_grad_launches": out[5]}

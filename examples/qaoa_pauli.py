@@ -5,10 +5,13 @@ PauliSum.  Parameters go in as angles and gradients come back as floats: no gate
 d gate / d parameter chain on the host.
 
   python examples/qaoa_pauli.py [--qubits 20] [--layers 10] [--iters 100] [--precision f64]
+                                [--cost-layer]
 
 Per layer a ZZ rotation on every bond of the ring with theta = 2 g and an X rotation on every qubit
 with theta = 2 b: the gates exp(-i g ZZ) and exp(-i b X) vqe_pauli.py writes as matrices, so the same
-parameters give the same energy and the same gradient."""
+parameters give the same energy and the same gradient.  With --cost-layer each layer's bonds are
+one diagonal Pauli layer exp(-i theta/2 sum ZZ) (DenseCircuit.add_var_pauli_evolution): one pass
+over the state per layer and direction instead of one per bond."""
 import argparse
 import sys
 import time
@@ -33,32 +36,36 @@ def hamiltonian(n, field=1.0):
                     + [(-field, f"X{i}") for i in range(n)])
 
 
-def build(n, layers, precision):
+def build(n, layers, precision, cost_layer=False):
     c = DenseCircuit(n, precision)
     c.set_state_from_vector(np.ones(1 << n, dtype=c.dtype) / np.sqrt(1 << n))
     for _ in range(layers):
-        for i, j in bonds(n):
-            c.add_var_pauli_rotation(f"Z{i} Z{j}")
+        if cost_layer:
+            c.add_var_pauli_evolution(PauliSum(n, [(1.0, f"Z{i} Z{j}") for i, j in bonds(n)]))
+        else:
+            for i, j in bonds(n):
+                c.add_var_pauli_rotation(f"Z{i} Z{j}")
         for i in range(n):
             c.add_var_pauli_rotation(f"X{i}")
     c.get_observable_op_with_grad(hamiltonian(n))
     return c
 
 
-def angles_of(params, n):
-    """The rotations' angles in instruction order: theta = 2 g on the bonds, 2 b on the sites."""
-    nb = len(bonds(n))
+def angles_of(params, n, cost_layer=False):
+    """The rotations' angles in instruction order: theta = 2 g on the bonds (once for a cost
+    layer), 2 b on the sites."""
+    nb = 1 if cost_layer else len(bonds(n))
     angles = []
     for layer in range(len(params) // 2):
         angles += [2.0 * float(params[2 * layer])] * nb + [2.0 * float(params[2 * layer + 1])] * n
     return angles
 
 
-def loss_and_grad(c, params, n):
+def loss_and_grad(c, params, n, cost_layer=False):
     """E = <psi|H|psi> and its gradient in the real parameters: d theta / d parameter = 2 times
     the sum of dE/dtheta over the parameter's rotations."""
-    nb = len(bonds(n))
-    angles = angles_of(params, n)
+    nb = 1 if cost_layer else len(bonds(n))
+    angles = angles_of(params, n, cost_layer)
     (energy,) = c.forward([], angles)
     dtheta = c.backward([1.0], [], angles)
     grad = np.zeros(len(params))
@@ -78,15 +85,17 @@ def main():
     ap.add_argument("--iters", type=int, default=100)
     ap.add_argument("--precision", default="f64", choices=["f32", "f64"])
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--cost-layer", action="store_true",
+                    help="one diagonal Pauli layer per layer of bonds")
     args = ap.parse_args()
     n = args.qubits
-    c = build(n, args.layers, args.precision)
+    c = build(n, args.layers, args.precision, args.cost_layer)
     params = np.random.default_rng(args.seed).normal(size=2 * args.layers)
     calls = [0]
 
     def loss_val_and_grad(p):
         calls[0] += 1
-        return loss_and_grad(c, p, n)
+        return loss_and_grad(c, p, n, args.cost_layer)
 
     start = time.time()
     result = minimize(loss_val_and_grad, params, method="L-BFGS-B", jac=True,

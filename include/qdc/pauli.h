@@ -73,6 +73,39 @@ const char* qdc_pauli_rot_reverse(qdc_complex* fwd, qdc_complex* bwd, unsigned l
                                   unsigned long long zmask, double theta, size_t n,
                                   double* dtheta);
 
+/* Diagonal Pauli layers (csrc/qdc_paulilayer.hpp): K rotations about Z-only strings
+ * P_k = Z^{zmask[k]} (any weight, zmask = 0 and duplicates allowed) in one pass over the state,
+ *     U = exp(-i/2 sum_k theta[k] P_k),  (U psi)[i] = e^{-i phi(i)} psi[i],
+ *     phi(i) = 1/2 sum_k theta[k] (-1)^popcount(i & zmask[k]),
+ * the product of qdc_pauli_rot(theta[k], 0, zmask[k]) in any order.  The phase is summed exactly
+ * in fixed point (theta / 4 pi rounded once to 2^-32 turns in f32, 2^-64 in f64).  A launch
+ * carries 128 terms (32 when it reduces gradients); larger layers take several passes.
+ * Errors: "The layer has no terms.", "pos is out of the bound.", "Pauli coefficients must be
+ * finite." (a non-finite theta), "fwd and bwd must be different states."; for NULL arguments
+ * "The layer has no masks.", "The layer has no angles." and "A gradient needs a bwd state."
+ * (dtheta without bwd). */
+
+/* state <- U state */
+const char* qdc_pauli_layer(qdc_complex* state, const unsigned long long* zmask,
+                            const double* theta, size_t terms, size_t n);
+
+/* One reverse step, in one pass over both states: fwd <- e^{+i phi} fwd (uncompute), bwd <-
+ * e^{-i phi} bwd (pull-back, U^T = U), dtheta[k] += dL/dtheta_k = 1/2 Im sum_i s_k(i) bwd[i] fwd[i]
+ * for k < terms (qdc_pauli_rot_reverse's convention; one stream synchronisation for up to
+ * 1024 terms, one more per further 1024).
+ * bwd == NULL: uncompute only (dtheta must be NULL).  dtheta == NULL: constant layer.  The same
+ * call returns the same bits every time. */
+const char* qdc_pauli_layer_reverse(qdc_complex* fwd, qdc_complex* bwd,
+                                    const unsigned long long* zmask, const double* theta,
+                                    size_t terms, size_t n, double* dtheta);
+
+/* Host only, no GPU: out[0..5] = {L (log2 of the amplitudes of a span), low-mask groups (distinct
+ * zmask mod 2^L), terms with a high part (zmask >= 2^L), forward launches, reverse launches
+ * without gradient, reverse launches with gradient}.  Returns the number of groups, SIZE_MAX on
+ * invalid arguments. */
+size_t qdc_pauli_layer_plan(const unsigned long long* zmask, size_t terms, size_t n,
+                            unsigned* out);
+
 #ifdef __cplusplus
 }
 #endif
