@@ -2,7 +2,8 @@
 //
 // Build (see Makefile): hipcc -O3 --offload-arch=gfx950 -fPIC -shared [-DQDC_F64]
 // Exports: the 18 reference primitives (include/qdc/primitives.h), their extensions
-// (include/qdc/dense.h, include/qdc/pauli.h) and the circuit runtime (include/qdc/circuit.h).  Everything else has hidden visibility.
+// (include/qdc/dense.h, include/qdc/pauli.h, include/qdc/sample.h) and the circuit runtime
+// (include/qdc/circuit.h).  Everything else has hidden visibility.
 #include "qdc_circuit.hpp"
 #include "qdc_primitives.hpp"
 #include "qdc_spec.hpp"

@@ -12,12 +12,14 @@
 #include "qdc/circuit.h"
 #include "qdc/dense.h"
 #include "qdc/pauli.h"
+#include "qdc/sample.h"
 #include "qdc_device.hpp"
 #include "qdc_qk.hpp"
 #include "qdc_qkgrad.hpp"
 #include "qdc_pauli.hpp"
 #include "qdc_paulirot.hpp"
 #include "qdc_paulilayer.hpp"
+#include "qdc_sample.hpp"
 
 namespace qdc {
 
@@ -478,6 +480,37 @@ __attribute__((visibility("default"))) size_t qdc_pauli_layer_plan(
   const unsigned v[6] = {qdc::PL_L, P.groups, P.high, P.fwd, P.rev, P.rev_grad};
   for (int i = 0; i < 6; ++i) out[i] = v[i];
   return P.groups;
+}
+
+// ---- sampling from |psi|^2 (include/qdc/sample.h, qdc_sample.hpp) ----------------------------
+
+__attribute__((visibility("default"))) const char* qdc_sample(
+    const qdc_complex* state, size_t n, const double* u, size_t shots, unsigned long long* out,
+    double* norm2) {
+  QDC_ABI_BEGIN
+  if (n > 40) return qdc::fail("pos is out of the bound.");
+  QDC_TRY(qdc::sample_check_uniforms(u, shots));
+  if (shots > 0 && !out) return qdc::fail("The sample has no output buffers.");
+  static qdc::SampleScratch scratch[qdc::ABI_MAX_DEVICES];  // guarded by the ABI mutex
+  return qdc::sample(ctx, reinterpret_cast<const qdc::cx*>(state), (uint32_t)n, u, shots, out,
+                     norm2, scratch[ctx.device]);
+}
+
+// host only: no context, no device
+__attribute__((visibility("default"))) size_t qdc_sample_plan(size_t n, unsigned* out) {
+  if (!out || n > 40) return SIZE_MAX;
+  const qdc::SamplePlan P = qdc::sample_plan(n);
+  const unsigned v[4] = {qdc::SAMPLE_G, (unsigned)P.segments, qdc::SAMPLE_SPAN,
+                         (unsigned)P.segments};
+  for (int i = 0; i < 4; ++i) out[i] = v[i];
+  return (size_t)P.segments;
+}
+
+// host only: no context, no device
+__attribute__((visibility("default"))) const char* qdc_sample_assign(
+    const double* seg_sums, size_t segments, const double* u, size_t shots,
+    unsigned long long* seg, double* resid, unsigned long long* perm, double* total) {
+  return qdc::sample_assign(seg_sums, segments, u, shots, seg, resid, perm, total);
 }
 
 __attribute__((visibility("default"))) const char* qdc_abi_sync(void) {

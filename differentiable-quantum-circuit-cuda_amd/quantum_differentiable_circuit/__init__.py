@@ -28,7 +28,7 @@ from .observable import PauliSum, layer_angles, layer_masks, pauli_layer_plan, p
 __all__ = ["Circuit", "Circuit32", "Circuit64", "QuantizedTensor", "PanicException",
            "get_q1_grad", "get_q2_grad", "get_q2_grad_diag", "get_qk_grad", "data_transfer",
            "PauliSum", "pauli_inject", "pauli_rot_reverse", "pauli_layer_reverse", "pauli_layer_plan",
-           "circuit_class",
+           "sample_plan", "sample_assign", "circuit_class",
            "plan", "unpermute", "get_hadamard", "get_cnot"]
 
 # enum Instruction order (src/circuit.rs:53-68) == enum qdc_kind (include/qdc/circuit.h)
@@ -761,6 +761,54 @@ class QuantizedTensor:
         check(self._lib.qdc_pauli_energy(self._p, *obs._args(), self.qubits_number, C.byref(e)))
         return float(e.value)
 
+    def norm_sq(self) -> float:
+        """N = sum_i |psi_i|^2 in double (qdc_sample with zero shots, include/qdc/sample.h): one
+        pass over the state, one host sync."""
+        n2 = C.c_double(0.0)
+        check(self._lib.qdc_sample(self._p, self.qubits_number, None, 0, None, C.byref(n2)))
+        return float(n2.value)
+
+    def sample(self, shots, seed=None, *, rng=None, uniforms=None, qubits=None) -> np.ndarray:
+        """``shots`` basis-state indices drawn from |psi|^2 / N (qdc_sample, include/qdc/sample.h),
+        a uint64 array; the state need not be normalised and is not changed.  The uniforms are
+        ``np.random.default_rng(seed).random(shots)``, or drawn from the Generator ``rng`` (which
+        advances), or ``uniforms`` as they are (float64 in [0, 1), one per shot): out[k] is the
+        first index whose cumulative probability exceeds uniforms[k] * N.  ``qubits=[q0, q1, ..]``
+        returns the marginal sample: bit b of each value is bit qubits[b] of the sampled index."""
+        shots = int(shots)
+        if shots < 0:
+            raise ValueError("shots must be >= 0")
+        if seed is not None and rng is not None:
+            raise PanicException("positions must be different.")
+        if qubits is not None:
+            qs = [int(q) for q in qubits]
+            if len(set(qs)) != len(qs) or any(q < 0 or q >= self.qubits_number for q in qs):
+                raise PanicException("pos is out of the bound.")
+        if uniforms is not None:
+            if seed is not None or rng is not None:
+                raise PanicException("positions must be different.")
+            u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
+            if u.size != shots:
+                raise PanicException("The number of uniforms does not match the shots.")
+        else:
+            u = (rng if rng is not None else np.random.default_rng(seed)).random(shots)
+        out = np.empty(shots, np.uint64)
+        check(self._lib.qdc_sample(self._p, self.qubits_number,
+                                   u.ctypes.data_as(C.POINTER(C.c_double)), shots,
+                                   out.ctypes.data_as(C.POINTER(C.c_ulonglong)), None))
+        if qubits is None:
+            return out
+        m = np.zeros(shots, np.uint64)
+        for b, q in enumerate(qs):
+            m |= ((out >> np.uint64(q)) & np.uint64(1)) << np.uint64(b)
+        return m
+
+    def sample_counts(self, shots, seed=None, *, rng=None, uniforms=None, qubits=None):
+        """``(values, counts)`` of ``sample(...)``: the distinct sampled values, ascending, and how
+        often each came up."""
+        return np.unique(self.sample(shots, seed, rng=rng, uniforms=uniforms, qubits=qubits),
+                         return_counts=True)
+
     def apply_pauli_rotation(self, ops, theta):
         """state <- exp(-i theta/2 P) state for the Pauli string ``ops`` (``"X0 Y3 Z12"`` or a
         sequence of ``(qubit, letter)``; qdc_pauli_rot, include/qdc/pauli.h): one pass over the
@@ -806,6 +854,38 @@ class QuantizedTensor:
         d = np.zeros(16, self.dtype)
         check(self._lib.get_q2density(self._p, ptr(d), pos2, pos1, self.qubits_number))
         return d
+
+
+def sample_plan(qubits_number, precision=None):
+    """The geometry of ``QuantizedTensor.sample`` on ``qubits_number`` qubits (qdc_sample_plan,
+    host only): ``{"G", "segments", "span", "locate_blocks"}`` — a segment is 2^G amplitudes (one
+    segment below that), a span the amplitudes a block scans at a time, ``locate_blocks`` the
+    most blocks the second pass launches.  None where the library rejects the size."""
+    lib = load(precision or default_precision())
+    out = (C.c_uint * 4)()
+    k = lib.qdc_sample_plan(int(qubits_number), out)
+    if k == C.c_size_t(-1).value:
+        return None
+    return {"G": out[0], "segments": out[1], "span": out[2], "locate_blocks": out[3]}
+
+
+def sample_assign(seg_sums, uniforms, precision=None):
+    """The host step between the two passes of ``sample`` (qdc_sample_assign, host only):
+    ``(seg, resid, perm, total)`` — for every uniform, in the caller's order, the segment it falls
+    in and the residual inside it; ``perm`` the processing order (segments ascending, residuals
+    ascending inside one); ``total`` the sum N of the segment sums."""
+    lib = load(precision or default_precision())
+    ss = np.ascontiguousarray(seg_sums, dtype=np.float64).reshape(-1)
+    u = np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)
+    seg = np.zeros(u.size, np.uint64)
+    resid = np.zeros(u.size, np.float64)
+    perm = np.zeros(u.size, np.uint64)
+    total = C.c_double(0.0)
+    dp, up = C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+    check(lib.qdc_sample_assign(ss.ctypes.data_as(dp), ss.size, u.ctypes.data_as(dp), u.size,
+                                seg.ctypes.data_as(up), resid.ctypes.data_as(dp),
+                                perm.ctypes.data_as(up), C.byref(total)))
+    return seg, resid, perm, float(total.value)
 
 
 def data_transfer(src: QuantizedTensor, dst: QuantizedTensor):

@@ -31,6 +31,11 @@ and a variable layer's gradient is a float64 array of K (zeros before the first 
 scalar theta for a ``PauliSum`` H of Z strings, ``U = exp(-i theta/2 H)`` (theta_k = theta c_k,
 the QAOA cost layer); its gradient is the float ``sum_k c_k dtheta_k``.
 
+``get_sample_op(shots, seed, qubits)`` draws bitstrings from the state at its place
+(``state.sample``): not differentiable, like ``get_dens_op``.  ``run`` returns its uint64 array at
+its place among the outputs; ``forward`` and ``backward`` skip it.  An int seed gives the same
+sample on every ``run``, ``seed=None`` a fresh one.
+
 Gates are 1-D arrays of 4^k values (2^k x 2^k row-major, local index bit (k-1-b) = qubit
 positions[b]); densities come back as (2^k, 2^k) arrays and gradients as 1-D arrays in forward
 order.  At k = 1, 2 every call lands on the q1 / q2 kernels, so a circuit of 1- and 2-qubit
@@ -54,7 +59,7 @@ from . import (PanicException, PauliSum, QuantizedTensor, _real_angle, data_tran
 from .abi_circuit import _slice
 
 (CONST_GATE, VAR_GATE, DENSITY, DIFF_DENSITY, OBSERVABLE, DIFF_OBSERVABLE, CONST_ROT,
- VAR_ROT, CONST_LAYER, VAR_LAYER, CONST_EVOL, VAR_EVOL) = range(12)
+ VAR_ROT, CONST_LAYER, VAR_LAYER, CONST_EVOL, VAR_EVOL, SAMPLE) = range(13)
 _CONST_KINDS = (CONST_GATE, CONST_ROT, CONST_LAYER, CONST_EVOL)
 
 
@@ -130,6 +135,17 @@ class DenseCircuit:
     def add_const_pauli_evolution(self, h): self._push_evolution(CONST_EVOL, h)
     def add_var_pauli_evolution(self, h): self._push_evolution(VAR_EVOL, h)
 
+    def get_sample_op(self, shots, seed=None, qubits=None):
+        shots = int(shots)
+        if shots < 0:
+            raise ValueError("shots must be >= 0")
+        if qubits is not None:
+            qubits = tuple(int(q) for q in qubits)
+            if len(set(qubits)) != len(qubits) or \
+                    any(q < 0 or q >= self.state.qubits_number for q in qubits):
+                raise PanicException("pos is out of the bound.")
+        self.instructions.append((SAMPLE, (shots, seed, qubits)))
+
     @staticmethod
     def _layer_angles(kind, pos, entry):
         """The K angles of a layer instruction from its FIFO entry."""
@@ -168,6 +184,10 @@ class DenseCircuit:
             elif kind in (OBSERVABLE, DIFF_OBSERVABLE):
                 if kind == DIFF_OBSERVABLE or all_densities:
                     out.append(s.pauli_energy(pos))
+            elif kind == SAMPLE:
+                if all_densities:
+                    shots, seed, qubits = pos
+                    out.append(s.sample(shots, seed, qubits=qubits))
             elif kind == DIFF_DENSITY or all_densities:
                 c = 1 << len(pos)
                 out.append(s.get_qk_density(pos).reshape(c, c))
@@ -178,7 +198,8 @@ class DenseCircuit:
         return out
 
     def run(self, const_gates, var_gates):
-        """Every density matrix and every observable's energy, in instruction order."""
+        """Every density matrix, every observable's energy and every sample, in instruction
+        order."""
         return self._forward(const_gates, var_gates, True)
 
     def forward(self, const_gates, var_gates):

@@ -5,13 +5,15 @@ PauliSum.  Parameters go in as angles and gradients come back as floats: no gate
 d gate / d parameter chain on the host.
 
   python examples/qaoa_pauli.py [--qubits 20] [--layers 10] [--iters 100] [--precision f64]
-                                [--cost-layer]
+                                [--cost-layer] [--shots K]
 
 Per layer a ZZ rotation on every bond of the ring with theta = 2 g and an X rotation on every qubit
 with theta = 2 b: the gates exp(-i g ZZ) and exp(-i b X) vqe_pauli.py writes as matrices, so the same
 parameters give the same energy and the same gradient.  With --cost-layer each layer's bonds are
 one diagonal Pauli layer exp(-i theta/2 sum ZZ) (DenseCircuit.add_var_pauli_evolution): one pass
-over the state per layer and direction instead of one per bond."""
+over the state per layer and direction instead of one per bond.  With --shots K the optimised
+state is sampled K times on the device (QuantizedTensor.sample): the five most frequent
+bitstrings, and the sample mean of the cost -sum Z_i Z_j beside its expectation value."""
 import argparse
 import sys
 import time
@@ -77,6 +79,23 @@ def loss_and_grad(c, params, n, cost_layer=False):
     return energy, grad
 
 
+def report_sample(c, params, n, shots, seed, cost_layer=False):
+    """Sample the state the parameters prepare: the most frequent bitstrings (qubit 0 rightmost)
+    and the sample mean of the cost -sum Z_i Z_j beside <psi| -sum Z_i Z_j |psi>."""
+    c.forward([], angles_of(params, n, cost_layer))
+    values, counts = c.state.sample_counts(shots, seed=seed)
+    for k in np.argsort(-counts, kind="stable")[:5]:
+        print(f"Sampled {int(values[k]):0{n}b}: {int(counts[k])} of {shots}")
+    cost = np.zeros(values.size)
+    for i, j in bonds(n):
+        zz = ((values >> np.uint64(i)) ^ (values >> np.uint64(j))) & np.uint64(1)
+        cost -= 1.0 - 2.0 * zz.astype(np.float64)
+    mean = float(np.dot(cost, counts)) / shots
+    zpart = PauliSum(n, [(-1.0, f"Z{i} Z{j}") for i, j in bonds(n)])
+    print(f"Sample mean of -sum ZZ: {mean}")
+    print(f"Expectation of -sum ZZ: {c.state.pauli_energy(zpart)}")
+
+
 def main():
     from scipy.optimize import minimize
     ap = argparse.ArgumentParser()
@@ -87,6 +106,8 @@ def main():
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--cost-layer", action="store_true",
                     help="one diagonal Pauli layer per layer of bonds")
+    ap.add_argument("--shots", type=int, default=0,
+                    help="bitstrings to sample from the optimised state (0: none)")
     args = ap.parse_args()
     n = args.qubits
     c = build(n, args.layers, args.precision, args.cost_layer)
@@ -107,6 +128,8 @@ def main():
     print(f"Relative error: {abs(result.fun - exact_e) / abs(exact_e)}")
     print(f"Number of loss value and gradient calls: {calls[0]}")
     print(f"Time per loss value and gradient call: {(end - start) / calls[0]}")
+    if args.shots > 0:
+        report_sample(c, result.x, n, args.shots, args.seed, args.cost_layer)
 
 
 if __name__ == "__main__":
