@@ -69,18 +69,23 @@ struct ltab {
 };
 static_assert(sizeof(ltab) <= 3584, "the table travels in the kernel arguments (4 KiB)");
 
-// the slot pattern and the thread mask of a low mask m < 2^L
-constexpr uint32_t pl_pattern(uint32_t m) {
-  return (m & (uint32_t)(VEC - 1)) | (((m >> (8 + LV)) & (uint32_t)(PAULI_FU - 1)) << LV);
+// the slot pattern and the thread mask of a low mask m < 2^L.  lv = log2 of the index values a
+// chunk holds: LV for amplitudes, 0 where a chunk is one pair (qdc_paulixlayer.hpp, f32 at x = 1);
+// L = 10 + lv and a thread has PAULI_FU << lv slots.
+constexpr uint32_t pl_pattern(uint32_t m, uint32_t lv = LV) {
+  return (m & ((1u << lv) - 1u)) | (((m >> (8 + lv)) & (uint32_t)(PAULI_FU - 1)) << lv);
 }
-constexpr uint32_t pl_tmask(uint32_t m) { return (m >> LV) & 0xffu; }
+constexpr uint32_t pl_tmask(uint32_t m, uint32_t lv = LV) { return (m >> lv) & 0xffu; }
+constexpr uint32_t pl_span_bits(uint32_t lv = LV) { return PL_L - (uint32_t)LV + lv; }
 
 // ph[slot] = phi(i_hi, slot, t) in 2^-B turns.  Everything but the thread's sign is uniform.
+template <int NS>
 __device__ __forceinline__ void pl_phases(const ltab& T, uint32_t ihi, uint32_t t,
-                                          pfix (&ph)[PL_NS]) {
+                                          pfix (&ph)[NS]) {
+  static_assert(NS <= PL_NS && (NS & (NS - 1)) == 0, "the slots of a table");
   uint32_t g = 0, k = 0;
 #pragma unroll
-  for (int p = 0; p < PL_NS; ++p) {
+  for (int p = 0; p < NS; ++p) {
     pfix F = 0;
     const uint32_t ge = T.pg[p + 1];
     for (; g < ge; ++g) {
@@ -96,9 +101,9 @@ __device__ __forceinline__ void pl_phases(const ltab& T, uint32_t ihi, uint32_t 
   }
   // ph[s] <- sum_p (-1)^popcount(s & p) ph[p]
 #pragma unroll
-  for (int bit = 1; bit < PL_NS; bit <<= 1)
+  for (int bit = 1; bit < NS; bit <<= 1)
 #pragma unroll
-    for (int s = 0; s < PL_NS; ++s)
+    for (int s = 0; s < NS; ++s)
       if (!(s & bit)) {
         const pfix a = ph[s], b = ph[s | bit];
         ph[s] = a + b;
@@ -119,13 +124,14 @@ __device__ __forceinline__ cx pl_cis(pfix ph) {
 
 // A[k] += the span's share of sum_i s_k(i) q(i), k < T.nt <= PL_GCAP; A = the thread's column of
 // the block's accumulators in LDS, term k at A[256 k].  q is left transformed.
+template <int NS>
 __device__ __forceinline__ void pl_grad(const ltab& T, uint32_t ihi, uint32_t t,
-                                        real (&q)[PL_NS], real* A) {
+                                        real (&q)[NS], real* A) {
   // q[p] <- W_p = sum_s (-1)^popcount(s & p) q[s]
 #pragma unroll
-  for (int bit = 1; bit < PL_NS; bit <<= 1)
+  for (int bit = 1; bit < NS; bit <<= 1)
 #pragma unroll
-    for (int s = 0; s < PL_NS; ++s)
+    for (int s = 0; s < NS; ++s)
       if (!(s & bit)) {
         const real a = q[s], b = q[s | bit];
         q[s] = a + b;
@@ -133,7 +139,7 @@ __device__ __forceinline__ void pl_grad(const ltab& T, uint32_t ihi, uint32_t t,
       }
   uint32_t g = 0, k = 0;
 #pragma unroll
-  for (int p = 0; p < PL_NS; ++p) {
+  for (int p = 0; p < NS; ++p) {
     const uint32_t ge = T.pg[p + 1];
     for (; g < ge; ++g) {
       const uint32_t gi = T.gi[g], ke = gi & 0xffffu, tm = gi >> 16;
@@ -264,28 +270,30 @@ inline const char* pl_check(const unsigned long long* zm, const double* theta, s
 }
 
 // low mask of a term on n qubits (n < L: the whole mask)
-inline uint32_t pl_low(uint64_t z) { return (uint32_t)(z & ((1u << PL_L) - 1u)); }
+inline uint32_t pl_low(uint64_t z, uint32_t lv = LV) {
+  return (uint32_t)(z & ((1u << pl_span_bits(lv)) - 1u));
+}
 
 // The table of terms [k0, k1) (k1 - k0 <= PL_CAP), ordered by slot pattern, low mask and term
 // number; perm[j] = the term at table place j.  theta == nullptr: the shape only.
 inline void pl_table(const unsigned long long* zm, const double* theta, size_t k0, size_t k1,
-                     bool reverse, ltab& T, uint32_t* perm) {
+                     bool reverse, ltab& T, uint32_t* perm, uint32_t lv = LV) {
   T = ltab{};
   std::vector<uint32_t> ord(k1 - k0);
   for (size_t j = 0; j < ord.size(); ++j) ord[j] = (uint32_t)(k0 + j);
   std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
-    const uint32_t ma = pl_low(zm[a]), mb = pl_low(zm[b]);
-    return std::make_pair(pl_pattern(ma), ma) < std::make_pair(pl_pattern(mb), mb);
+    const uint32_t ma = pl_low(zm[a], lv), mb = pl_low(zm[b], lv);
+    return std::make_pair(pl_pattern(ma, lv), ma) < std::make_pair(pl_pattern(mb, lv), mb);
   });
   T.nt = (uint32_t)ord.size();
   uint32_t ng = 0;
   for (uint32_t j = 0; j < T.nt; ++j) {
     const uint64_t z = zm[ord[j]];
-    const uint32_t m = pl_low(z), p = pl_pattern(m);
-    if (j == 0 || pl_low(zm[ord[j - 1]]) != m) ++ng;  // a new group
-    T.gi[ng - 1] = (j + 1) | (pl_tmask(m) << 16);
+    const uint32_t m = pl_low(z, lv), p = pl_pattern(m, lv);
+    if (j == 0 || pl_low(zm[ord[j - 1]], lv) != m) ++ng;  // a new group
+    T.gi[ng - 1] = (j + 1) | (pl_tmask(m, lv) << 16);
     for (uint32_t pp = p + 1; pp <= (uint32_t)PL_NS; ++pp) T.pg[pp] = (uint16_t)ng;
-    T.zhi[j] = (uint32_t)(z >> PL_L);
+    T.zhi[j] = (uint32_t)(z >> pl_span_bits(lv));
     const pfix t = theta ? pl_fix(theta[ord[j]]) : (pfix)0;
     T.t[j] = reverse ? (pfix)0 - t : t;
     if (perm) perm[j] = ord[j];
@@ -295,12 +303,12 @@ inline void pl_table(const unsigned long long* zm, const double* theta, size_t k
 struct PauliLayerPlan {
   unsigned groups = 0, high = 0, fwd = 0, rev = 0, rev_grad = 0;
 };
-inline PauliLayerPlan pl_plan(const unsigned long long* zm, size_t terms) {
+inline PauliLayerPlan pl_plan(const unsigned long long* zm, size_t terms, uint32_t lv = LV) {
   PauliLayerPlan P;
   std::vector<uint32_t> low(terms);
   for (size_t k = 0; k < terms; ++k) {
-    low[k] = pl_low(zm[k]);
-    if ((zm[k] >> PL_L) != 0) ++P.high;
+    low[k] = pl_low(zm[k], lv);
+    if ((zm[k] >> pl_span_bits(lv)) != 0) ++P.high;
   }
   std::sort(low.begin(), low.end());
   P.groups = (unsigned)(std::unique(low.begin(), low.end()) - low.begin());
@@ -321,48 +329,62 @@ inline const char* pl_launch(Ctx& c, const char* name, double bytes, cx* f, cx* 
                         (uint32_t)std::min<uint64_t>((uint64_t)1 << n, VEC), out);
 }
 
+// How a layer's launches run: the diagonal kernel here, the paired ones in qdc_paulixlayer.hpp.
+struct PlDiag {
+  uint32_t lv = LV;
+  const char *fwd_name = "pauli_layer", *rev_name = "pauli_layer_rev";
+  uint32_t grid(uint32_t n, uint32_t cap) const { return pl_grid(n, cap); }
+  template <bool BWD, bool GRAD>
+  const char* launch(Ctx& c, const char* name, double bytes, cx* f, cx* b, const ltab& T,
+                     uint32_t n, uint32_t grid, cx* out) const {
+    return pl_launch<BWD, GRAD>(c, name, bytes, f, b, T, n, grid, out);
+  }
+};
+
 // s <- U s
-inline const char* pauli_layer(Ctx& c, cx* s, const unsigned long long* zm, const double* theta,
-                               size_t terms, uint32_t n) {
-  const uint32_t grid = pl_grid(n, 1u << 20);
+template <class R>
+inline const char* pl_forward(Ctx& c, const R& r, cx* s, const unsigned long long* zm,
+                              const double* theta, size_t terms, uint32_t n) {
+  const uint32_t grid = r.grid(n, 1u << 20);
   ltab T;
   for (size_t k0 = 0; k0 < terms; k0 += PL_CAP) {
-    pl_table(zm, theta, k0, std::min(terms, k0 + PL_CAP), false, T, nullptr);
-    QDC_TRY((pl_launch<false, false>(c, "pauli_layer", 2.0 * state_bytes(n), s, nullptr, T, n,
-                                     grid, nullptr)));
+    pl_table(zm, theta, k0, std::min(terms, k0 + PL_CAP), false, T, nullptr, r.lv);
+    QDC_TRY((r.template launch<false, false>(c, r.fwd_name, 2.0 * state_bytes(n), s, nullptr, T,
+                                             n, grid, nullptr)));
   }
   return nullptr;
 }
 
-// f <- U^-1 f; b <- U^T b (b != nullptr); dtheta[k] += dL/dtheta_k (dtheta != nullptr: one stream
+// f <- U^-1 f; b <- U^T b (b != nullptr); dtheta[k] += 1/2 sum s_k q (dtheta != nullptr: one stream
 // synchronisation per FIN_MAX reducing launches, FIN_MAX * PL_GCAP = 1024 terms).
-inline const char* pauli_layer_reverse(Ctx& c, cx* f, cx* b, const unsigned long long* zm,
-                                       const double* theta, size_t terms, uint32_t n,
-                                       double* dtheta) {
-  const char* name = "pauli_layer_rev";
+template <class R>
+inline const char* pl_reverse(Ctx& c, const R& r, cx* f, cx* b, const unsigned long long* zm,
+                              const double* theta, size_t terms, uint32_t n, double* dtheta) {
+  const char* name = r.rev_name;
   ltab T;
   if (!dtheta) {
-    const uint32_t grid = pl_grid(n, 1u << 20);
+    const uint32_t grid = r.grid(n, 1u << 20);
     for (size_t k0 = 0; k0 < terms; k0 += PL_CAP) {
-      pl_table(zm, theta, k0, std::min(terms, k0 + PL_CAP), true, T, nullptr);
+      pl_table(zm, theta, k0, std::min(terms, k0 + PL_CAP), true, T, nullptr, r.lv);
       if (b)
-        QDC_TRY((pl_launch<true, false>(c, name, 4.0 * state_bytes(n), f, b, T, n, grid, nullptr)));
+        QDC_TRY((r.template launch<true, false>(c, name, 4.0 * state_bytes(n), f, b, T, n, grid,
+                                                nullptr)));
       else
-        QDC_TRY((pl_launch<false, false>(c, name, 2.0 * state_bytes(n), f, nullptr, T, n, grid,
-                                         nullptr)));
+        QDC_TRY((r.template launch<false, false>(c, name, 2.0 * state_bytes(n), f, nullptr, T, n,
+                                                 grid, nullptr)));
     }
     return nullptr;
   }
-  const uint32_t grid = pl_grid(n, c.k.red_cap);
+  const uint32_t grid = r.grid(n, c.k.red_cap);
   const size_t nl = (terms + PL_GCAP - 1) / PL_GCAP;
   std::vector<uint32_t> perm(terms);
   for (size_t l0 = 0; l0 < nl; l0 += FIN_MAX) {
     const size_t l1 = std::min<size_t>(nl, l0 + FIN_MAX);
     for (size_t l = l0; l < l1; ++l) {
       const size_t k0 = l * PL_GCAP;
-      pl_table(zm, theta, k0, std::min(terms, k0 + PL_GCAP), true, T, perm.data() + k0);
+      pl_table(zm, theta, k0, std::min(terms, k0 + PL_GCAP), true, T, perm.data() + k0, r.lv);
       QDC_TRY(reduce_into(c, c.results, (uint32_t)(l - l0), 0, grid, [&](cx* out) {
-        return pl_launch<true, true>(c, name, 4.0 * state_bytes(n), f, b, T, n, grid, out);
+        return r.template launch<true, true>(c, name, 4.0 * state_bytes(n), f, b, T, n, grid, out);
       }));
     }
     QDC_TRY(c.flush());
@@ -378,6 +400,16 @@ inline const char* pauli_layer_reverse(Ctx& c, cx* f, cx* b, const unsigned long
     }
   }
   return nullptr;
+}
+
+inline const char* pauli_layer(Ctx& c, cx* s, const unsigned long long* zm, const double* theta,
+                               size_t terms, uint32_t n) {
+  return pl_forward(c, PlDiag{}, s, zm, theta, terms, n);
+}
+inline const char* pauli_layer_reverse(Ctx& c, cx* f, cx* b, const unsigned long long* zm,
+                                       const double* theta, size_t terms, uint32_t n,
+                                       double* dtheta) {
+  return pl_reverse(c, PlDiag{}, f, b, zm, theta, terms, n, dtheta);
 }
 
 }  // namespace qdc

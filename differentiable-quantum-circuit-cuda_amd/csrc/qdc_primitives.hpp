@@ -19,6 +19,7 @@
 #include "qdc_pauli.hpp"
 #include "qdc_paulirot.hpp"
 #include "qdc_paulilayer.hpp"
+#include "qdc_paulixlayer.hpp"
 #include "qdc_sample.hpp"
 
 namespace qdc {
@@ -480,6 +481,57 @@ __attribute__((visibility("default"))) size_t qdc_pauli_layer_plan(
   const unsigned v[6] = {qdc::PL_L, P.groups, P.high, P.fwd, P.rev, P.rev_grad};
   for (int i = 0; i < 6; ++i) out[i] = v[i];
   return P.groups;
+}
+
+// ---- Pauli layers with a shared X/Y footprint (qdc_paulixlayer.hpp) ----------------------------
+
+__attribute__((visibility("default"))) const char* qdc_pauli_xlayer(
+    qdc_complex* state, unsigned long long xmask, const unsigned long long* zmask,
+    const double* theta, size_t terms, size_t n) {
+  if (xmask == 0) return qdc_pauli_layer(state, zmask, theta, terms, n);
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  qdc::PxLayer P;
+  QDC_TRY(qdc::pxl_make(xmask, zmask, theta, terms, n, P));
+  if (!theta) return qdc::fail("The layer has no angles.");
+  return qdc::pauli_xlayer(ctx, reinterpret_cast<qdc::cx*>(state), P, theta, (uint32_t)n);
+}
+
+__attribute__((visibility("default"))) const char* qdc_pauli_xlayer_reverse(
+    qdc_complex* fwd, qdc_complex* bwd, unsigned long long xmask,
+    const unsigned long long* zmask, const double* theta, size_t terms, size_t n,
+    double* dtheta) {
+  if (xmask == 0) return qdc_pauli_layer_reverse(fwd, bwd, zmask, theta, terms, n, dtheta);
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  qdc::PxLayer P;
+  QDC_TRY(qdc::pxl_make(xmask, zmask, theta, terms, n, P));
+  if (!theta) return qdc::fail("The layer has no angles.");
+  if (fwd == bwd) return qdc::fail("fwd and bwd must be different states.");
+  if (!bwd && dtheta) return qdc::fail("A gradient needs a bwd state.");
+  return qdc::pauli_xlayer_reverse(ctx, reinterpret_cast<qdc::cx*>(fwd),
+                                   reinterpret_cast<qdc::cx*>(bwd), P, theta, (uint32_t)n, dtheta);
+}
+
+// host only: no context, no device
+__attribute__((visibility("default"))) size_t qdc_pauli_xlayer_plan(
+    unsigned long long xmask, const unsigned long long* zmask, size_t terms, size_t n,
+    unsigned* out) {
+  if (!out || n > 40) return SIZE_MAX;
+  if (xmask == 0) {
+    const size_t k = qdc_pauli_layer_plan(zmask, terms, n, out);
+    if (k == SIZE_MAX) return k;
+    const unsigned v[6] = {out[0], ~0u, out[1], out[3], out[4], out[5]};
+    for (int i = 0; i < 6; ++i) out[i] = v[i];
+    return k;
+  }
+  qdc::PxLayer P;
+  if (qdc::pxl_make(xmask, zmask, nullptr, terms, n, P)) return SIZE_MAX;
+  const qdc::PauliLayerPlan L = qdc::pl_plan(P.zr.data(), terms, P.lv);
+  const unsigned v[6] = {qdc::pl_span_bits(P.lv), P.self ? ~0u : P.hb, L.groups, L.fwd, L.rev,
+                         L.rev_grad};
+  for (int i = 0; i < 6; ++i) out[i] = v[i];
+  return L.groups;
 }
 
 // ---- sampling from |psi|^2 (include/qdc/sample.h, qdc_sample.hpp) ----------------------------

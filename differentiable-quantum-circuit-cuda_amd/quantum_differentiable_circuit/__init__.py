@@ -23,11 +23,14 @@ import numpy as np
 from .common_gates import get_cnot, get_hadamard  # noqa: E402  (common_gates.rs)
 from ._native import (PanicException, KernelStat, PlanOp, check, default_precision, load,
                       ptr, PRECISIONS)
-from .observable import PauliSum, layer_angles, layer_masks, pauli_layer_plan, pauli_masks
+from .observable import (PauliSum, excitation, ladder_terms, layer_angles, layer_masks,
+                         pauli_layer_plan, pauli_masks, pauli_xlayer_plan, xevolution_masks,
+                         xlayer_masks)
 
 __all__ = ["Circuit", "Circuit32", "Circuit64", "QuantizedTensor", "PanicException",
            "get_q1_grad", "get_q2_grad", "get_q2_grad_diag", "get_qk_grad", "data_transfer",
            "PauliSum", "pauli_inject", "pauli_rot_reverse", "pauli_layer_reverse", "pauli_layer_plan",
+           "pauli_xlayer_reverse", "pauli_xlayer_plan", "xlayer_masks", "excitation", "ladder_terms",
            "sample_plan", "sample_assign", "circuit_class",
            "plan", "unpermute", "get_hadamard", "get_cnot"]
 
@@ -826,6 +829,17 @@ class QuantizedTensor:
                                         t.ctypes.data_as(C.POINTER(C.c_double)), z.size,
                                         self.qubits_number))
 
+    def apply_pauli_xlayer(self, strings, thetas):
+        """state <- exp(-i/2 sum_k thetas[k] P_k) state for commuting strings P_k that share their
+        X/Y positions (each in the forms of ``apply_pauli_rotation``, or ``(xmask, zmasks)``;
+        qdc_pauli_xlayer, include/qdc/pauli.h): the product of the K rotations in one pass over
+        the state per 128 strings.  Z-only strings take the diagonal layer."""
+        x, z = xlayer_masks(self.qubits_number, strings)
+        t = layer_angles(thetas, z.size)
+        check(self._lib.qdc_pauli_xlayer(self._p, x, z.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                         t.ctypes.data_as(C.POINTER(C.c_double)), z.size,
+                                         self.qubits_number))
+
     def apply_q2_gate_inv(self, gate, pos2, pos1):
         g = self._gate(gate, 16)
         self._pos2(pos2, pos1)
@@ -990,4 +1004,27 @@ def pauli_layer_reverse(fwd, bwd, strings, thetas, want_grad=True) -> np.ndarray
         raise PanicException("fwd and bwd have different lengths.")
     dp = d.ctypes.data_as(C.POINTER(C.c_double)) if want_grad else None
     check(fwd._lib.qdc_pauli_layer_reverse(fwd._p, bwd._p, zp, tp, z.size, fwd.qubits_number, dp))
+    return d
+
+
+def pauli_xlayer_reverse(fwd, bwd, strings, thetas, want_grad=True) -> np.ndarray:
+    """One reverse step of ``fwd.apply_pauli_xlayer(strings, thetas)`` (qdc_pauli_xlayer_reverse),
+    in one pass over both states per 32 strings (128 without gradients): fwd <- U(-thetas) fwd,
+    bwd <- U^T bwd, and dL/dtheta_k = 1/2 Im sum_i bwd[i] (P_k fwd)[i] (fwd, bwd as received) as a
+    float64 array of K values; zeros when ``want_grad`` is false (a constant layer) or ``bwd`` is
+    None (no cotangent yet: only the uncompute)."""
+    x, z = xlayer_masks(fwd.qubits_number, strings)
+    t = layer_angles(thetas, z.size)
+    zp = z.ctypes.data_as(C.POINTER(C.c_ulonglong))
+    tp = t.ctypes.data_as(C.POINTER(C.c_double))
+    d = np.zeros(z.size, np.float64)
+    if bwd is None:
+        check(fwd._lib.qdc_pauli_xlayer_reverse(fwd._p, None, x, zp, tp, z.size,
+                                                fwd.qubits_number, None))
+        return d
+    if fwd.qubits_number != bwd.qubits_number:
+        raise PanicException("fwd and bwd have different lengths.")
+    dp = d.ctypes.data_as(C.POINTER(C.c_double)) if want_grad else None
+    check(fwd._lib.qdc_pauli_xlayer_reverse(fwd._p, bwd._p, x, zp, tp, z.size, fwd.qubits_number,
+                                            dp))
     return d

@@ -42,6 +42,7 @@ RUNTIME = (
     "qdc_pauli_energy", "qdc_pauli_inject", "qdc_pauli_plan",
     "qdc_pauli_rot", "qdc_pauli_rot_reverse",
     "qdc_pauli_layer", "qdc_pauli_layer_reverse", "qdc_pauli_layer_plan",
+    "qdc_pauli_xlayer", "qdc_pauli_xlayer_reverse", "qdc_pauli_xlayer_plan",
     "qdc_sample", "qdc_sample_plan", "qdc_sample_assign",
 )
 
@@ -138,6 +139,12 @@ def _proto(lib):
         "qdc_pauli_layer_reverse": (_E, [_P, _P, C.POINTER(C.c_ulonglong),
                                          C.POINTER(C.c_double), _S, _S, C.POINTER(C.c_double)]),
         "qdc_pauli_layer_plan": (_S, [C.POINTER(C.c_ulonglong), _S, _S, C.POINTER(C.c_uint)]),
+        "qdc_pauli_xlayer": (_E, [_P, C.c_ulonglong, C.POINTER(C.c_ulonglong),
+                                  C.POINTER(C.c_double), _S, _S]),
+        "qdc_pauli_xlayer_reverse": (_E, [_P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong),
+                                          C.POINTER(C.c_double), _S, _S, C.POINTER(C.c_double)]),
+        "qdc_pauli_xlayer_plan": (_S, [C.c_ulonglong, C.POINTER(C.c_ulonglong), _S, _S,
+                                       C.POINTER(C.c_uint)]),
         "qdc_sample": (_E, [_P, _S, C.POINTER(C.c_double), _S, C.POINTER(C.c_ulonglong),
                             C.POINTER(C.c_double)]),
         "qdc_sample_plan": (_S, [_S, C.POINTER(C.c_uint)]),

@@ -31,6 +31,13 @@ and a variable layer's gradient is a float64 array of K (zeros before the first 
 scalar theta for a ``PauliSum`` H of Z strings, ``U = exp(-i theta/2 H)`` (theta_k = theta c_k,
 the QAOA cost layer); its gradient is the float ``sum_k c_k dtheta_k``.
 
+``add_const_pauli_xlayer`` / ``add_var_pauli_xlayer``, ``add_const_pauli_xevolution`` /
+``add_var_pauli_xevolution`` are the same two instructions for commuting strings that share their
+X/Y positions (``apply_pauli_xlayer`` / ``pauli_xlayer_reverse``), and
+``add_const_excitation(occ, virt)`` / ``add_var_excitation(occ, virt)`` is the xevolution of
+``excitation(n, occ, virt)``: ``exp(theta/2 (tau - tau^dagger))``, a fermionic excitation under
+Jordan-Wigner in one pass.
+
 ``get_sample_op(shots, seed, qubits)`` draws bitstrings from the state at its place
 (``state.sample``): not differentiable, like ``get_dens_op``.  ``run`` returns its uint64 array at
 its place among the outputs; ``forward`` and ``backward`` skip it.  An int seed gives the same
@@ -53,14 +60,17 @@ from typing import List
 
 import numpy as np
 
-from . import (PanicException, PauliSum, QuantizedTensor, _real_angle, data_transfer,
+from . import (PanicException, PauliSum, QuantizedTensor, _real_angle, data_transfer, excitation,
                get_qk_grad, layer_angles, layer_masks, pauli_inject, pauli_layer_reverse,
-               pauli_masks, pauli_rot_reverse)
+               pauli_masks, pauli_rot_reverse, pauli_xlayer_reverse, xevolution_masks,
+               xlayer_masks)
 from .abi_circuit import _slice
 
 (CONST_GATE, VAR_GATE, DENSITY, DIFF_DENSITY, OBSERVABLE, DIFF_OBSERVABLE, CONST_ROT,
- VAR_ROT, CONST_LAYER, VAR_LAYER, CONST_EVOL, VAR_EVOL, SAMPLE) = range(13)
-_CONST_KINDS = (CONST_GATE, CONST_ROT, CONST_LAYER, CONST_EVOL)
+ VAR_ROT, CONST_LAYER, VAR_LAYER, CONST_EVOL, VAR_EVOL, SAMPLE, CONST_XLAYER, VAR_XLAYER,
+ CONST_XEVOL, VAR_XEVOL) = range(17)
+_CONST_KINDS = (CONST_GATE, CONST_ROT, CONST_LAYER, CONST_EVOL, CONST_XLAYER, CONST_XEVOL)
+_XLAYER_KINDS = (CONST_XLAYER, VAR_XLAYER, CONST_XEVOL, VAR_XEVOL)
 
 
 
@@ -135,6 +145,39 @@ class DenseCircuit:
     def add_const_pauli_evolution(self, h): self._push_evolution(CONST_EVOL, h)
     def add_var_pauli_evolution(self, h): self._push_evolution(VAR_EVOL, h)
 
+    def _push_xlayer(self, kind, strings):
+        if not (isinstance(strings, tuple) and len(strings) == 2
+                and isinstance(strings[1], np.ndarray)):
+            strings = tuple(s if isinstance(s, str) else tuple(s) for s in strings)
+        if len(strings) == 0:
+            raise PanicException("The layer has no terms.")
+        x, zmasks = xlayer_masks(self.state.qubits_number, strings)
+        if zmasks.size == 0:
+            raise PanicException("The layer has no terms.")
+        self.instructions.append((kind, ((x, zmasks), None)))
+
+    def add_const_pauli_xlayer(self, strings): self._push_xlayer(CONST_XLAYER, strings)
+    def add_var_pauli_xlayer(self, strings): self._push_xlayer(VAR_XLAYER, strings)
+
+    def _push_xevolution(self, kind, h):
+        if not isinstance(h, PauliSum):
+            raise TypeError("argument 'H': expected a PauliSum")
+        if h.qubits_number != self.state.qubits_number:
+            raise PanicException("The observable and the tensor have different sizes.")
+        if len(h) == 0:
+            raise PanicException("The layer has no terms.")
+        x, zmasks, coeffs = xevolution_masks(h)
+        self.instructions.append((kind, ((x, zmasks), coeffs)))
+
+    def add_const_pauli_xevolution(self, h): self._push_xevolution(CONST_XEVOL, h)
+    def add_var_pauli_xevolution(self, h): self._push_xevolution(VAR_XEVOL, h)
+
+    def add_const_excitation(self, occ, virt):
+        self._push_xevolution(CONST_XEVOL, excitation(self.state.qubits_number, occ, virt))
+
+    def add_var_excitation(self, occ, virt):
+        self._push_xevolution(VAR_XEVOL, excitation(self.state.qubits_number, occ, virt))
+
     def get_sample_op(self, shots, seed=None, qubits=None):
         shots = int(shots)
         if shots < 0:
@@ -149,10 +192,10 @@ class DenseCircuit:
     @staticmethod
     def _layer_angles(kind, pos, entry):
         """The K angles of a layer instruction from its FIFO entry."""
-        zmasks, coeffs = pos
-        if kind in (CONST_EVOL, VAR_EVOL):
+        masks, coeffs = pos
+        if coeffs is not None:
             return _real_angle(entry) * coeffs
-        return layer_angles(entry, zmasks.size)
+        return layer_angles(entry, (masks[1] if kind in _XLAYER_KINDS else masks).size)
 
     # --- forward --------------------------------------------------------------------------
     def _forward(self, const_gates, var_gates, all_densities) -> List[np.ndarray]:
@@ -181,6 +224,12 @@ class DenseCircuit:
                     word = "constant" if kind in _CONST_KINDS else "variable"
                     raise PanicException(f"The number of {word} gates is less than required.")
                 s.apply_pauli_layer(pos[0], self._layer_angles(kind, pos, pool.popleft()))
+            elif kind in _XLAYER_KINDS:
+                pool = cg if kind in _CONST_KINDS else vg
+                if not pool:
+                    word = "constant" if kind in _CONST_KINDS else "variable"
+                    raise PanicException(f"The number of {word} gates is less than required.")
+                s.apply_pauli_xlayer(pos[0], self._layer_angles(kind, pos, pool.popleft()))
             elif kind in (OBSERVABLE, DIFF_OBSERVABLE):
                 if kind == DIFF_OBSERVABLE or all_densities:
                     out.append(s.pauli_energy(pos))
@@ -248,6 +297,17 @@ class DenseCircuit:
                 if kind == VAR_LAYER:
                     grads.appendleft(d)
                 elif kind == VAR_EVOL:
+                    grads.appendleft(float(np.dot(pos[1], d)))
+            elif kind in _XLAYER_KINDS:
+                pool = cg if kind in _CONST_KINDS else vg
+                if not pool:
+                    raise PanicException("The number of gates is less than required.")
+                d = pauli_xlayer_reverse(fwd, bwd, pos[0],
+                                         self._layer_angles(kind, pos, pool.pop()),
+                                         want_grad=kind in (VAR_XLAYER, VAR_XEVOL))
+                if kind == VAR_XLAYER:
+                    grads.appendleft(d)
+                elif kind == VAR_XEVOL:
                     grads.appendleft(float(np.dot(pos[1], d)))
             elif kind == DIFF_DENSITY:
                 if not dens:

@@ -234,3 +234,108 @@ def pauli_layer_plan(qubits_number, strings, precision=None):
         return None
     return {"L": out[0], "groups": out[1], "high_terms": out[2], "forward_launches": out[3],
             "reverse_launches": out[4], "reverse_grad_launches": out[5]}
+
+
+def _commute_check(x, zs):
+    """Strings (x, z_k) with one x commute iff every nY_k = popcount(x & z_k) has one parity."""
+    par = {bin(x & int(z)).count("1") & 1 for z in zs}
+    if len(par) > 1:
+        raise PanicException("The strings of a layer must commute.")
+
+
+def xlayer_masks(qubits_number: int, strings):
+    """``(xmask, zmasks)`` of a Pauli layer whose strings share their X/Y positions and commute
+    (``apply_pauli_xlayer``): ``strings`` is a sequence of Pauli strings in the forms
+    ``pauli_masks`` accepts; a pair ``(xmask, uint64 array of zmasks)`` is taken as the masks
+    themselves (the library checks them)."""
+    if isinstance(strings, tuple) and len(strings) == 2 and isinstance(strings[1], np.ndarray) \
+            and strings[1].dtype == np.uint64 and strings[1].ndim == 1:
+        return int(strings[0]), np.ascontiguousarray(strings[1])
+    if isinstance(strings, str):
+        raise PanicException("a Pauli layer takes a sequence of strings.")
+    x, zs = None, []
+    for ops in strings:
+        xk, zk = pauli_masks(qubits_number, ops)
+        if x is not None and xk != x:
+            raise PanicException("The strings of a layer must share their X/Y positions.")
+        x = xk
+        zs.append(zk)
+    _commute_check(x or 0, zs)
+    return x or 0, np.array(zs, dtype=np.uint64)
+
+
+def xevolution_masks(h: PauliSum):
+    """``(xmask, zmasks, coeffs)`` of a ``PauliSum`` whose terms share their X/Y positions and
+    commute (``add_var_pauli_xevolution``)."""
+    if np.any(h.xmasks != h.xmasks[0]):
+        raise PanicException("The strings of a layer must share their X/Y positions.")
+    x = int(h.xmasks[0])
+    _commute_check(x, h.zmasks)
+    return x, h.zmasks.copy(), h.coeffs.copy()
+
+
+def pauli_xlayer_plan(qubits_number, strings, precision=None):
+    """The launch plan of a shared-footprint Pauli layer (qdc_pauli_xlayer_plan, host only):
+    ``{"L", "deleted_bit", "groups", "forward_launches", "reverse_launches",
+    "reverse_grad_launches"}``; ``deleted_bit`` is None for the diagonal (x = 0) and the
+    self-paired (f32, x = 1) forms.  ``strings`` as for ``apply_pauli_xlayer``.  None where the
+    library rejects the masks."""
+    from ._native import default_precision, load
+    lib = load(precision or default_precision())
+    x, zs = xlayer_masks(qubits_number, strings)
+    out = (C.c_uint * 6)()
+    k = lib.qdc_pauli_xlayer_plan(x, zs.ctypes.data_as(C.POINTER(C.c_ulonglong)), zs.size,
+                                  int(qubits_number), out)
+    if k == C.c_size_t(-1).value:
+        return None
+    return {"L": out[0], "deleted_bit": None if out[1] == 0xffffffff else out[1],
+            "groups": out[2], "forward_launches": out[3], "reverse_launches": out[4],
+            "reverse_grad_launches": out[5]}
+
+
+def _string_mul(a, b):
+    """(phase, (x, z)) of the product of two strings: with W(x, z) = X^x Z^z the string is
+    P = i^nY W, and W(x1, z1) W(x2, z2) = (-1)^popcount(z1 & x2) W(x1 ^ x2, z1 ^ z2)."""
+    (x1, z1), (x2, z2) = a, b
+    x, z = x1 ^ x2, z1 ^ z2
+    ny = bin(x1 & z1).count("1") + bin(x2 & z2).count("1") - bin(x & z).count("1")
+    return 1j ** (ny % 4) * (-1) ** (bin(z1 & x2).count("1") & 1), (x, z)
+
+
+def ladder_terms(qubits_number: int, ops):
+    """The product of Jordan-Wigner ladder operators as ``{(xmask, zmask): complex}``: ``ops`` is a
+    sequence of ``(mode, dagger)``, leftmost factor first, with
+    ``a_q = (prod_{r<q} Z_r) (X_q + i Y_q) / 2`` (qubit value 1 = occupied) and ``a_q^dagger`` its
+    adjoint.  Terms whose coefficients cancel are dropped."""
+    n = int(qubits_number)
+    out = {(0, 0): 1.0 + 0.0j}
+    for q, dagger in ops:
+        q = int(q)
+        if q < 0 or q >= n:
+            raise PanicException("pos is out of the bound.")
+        bit, low = 1 << q, (1 << q) - 1
+        factor = {(bit, low): 0.5, (bit, low | bit): -0.5j if dagger else 0.5j}
+        nxt = {}
+        for ka, ca in out.items():
+            for kb, cb in factor.items():
+                ph, key = _string_mul(ka, kb)
+                nxt[key] = nxt.get(key, 0.0) + ca * cb * ph
+        out = {k: c for k, c in nxt.items() if c != 0}
+    return out
+
+
+def excitation(qubits_number: int, occ, virt) -> PauliSum:
+    """The generator ``G = i (tau - tau^dagger)`` of a fermionic excitation under Jordan-Wigner,
+    ``tau = prod_{p in virt} a_p^dagger prod_{q in occ} a_q`` (``ladder_terms``): 2 / 8 / 32
+    strings for a single / double / triple excitation, with one X/Y footprint, all commuting.
+    ``exp(-i theta/2 G) = exp(theta/2 (tau - tau^dagger))``."""
+    occ, virt = [int(q) for q in occ], [int(p) for p in virt]
+    if len(occ) != len(virt) or not 1 <= len(occ) <= 3:
+        raise PanicException("an excitation takes 1, 2 or 3 occupied and as many virtual modes.")
+    if len(set(occ + virt)) != len(occ) + len(virt):
+        raise PanicException("positions must be different.")
+    tau = ladder_terms(qubits_number, [(p, True) for p in virt] + [(q, False) for q in occ])
+    # tau^dagger has the conjugate coefficients: i (c - conj c) = -2 Im c
+    terms = [(k, -2.0 * c.imag) for k, c in tau.items() if c.imag != 0.0]
+    return PauliSum.from_masks(qubits_number, [c for _, c in terms], [k[0] for k, _ in terms],
+                               [k[1] for k, _ in terms])

@@ -106,6 +106,42 @@ const char* qdc_pauli_layer_reverse(qdc_complex* fwd, qdc_complex* bwd,
 size_t qdc_pauli_layer_plan(const unsigned long long* zmask, size_t terms, size_t n,
                             unsigned* out);
 
+/* Pauli layers with a shared X/Y footprint (csrc/qdc_paulixlayer.hpp): K rotations about the
+ * strings P_k = (xmask, zmask[k]), one xmask for all of them, in one pass over the state,
+ *     U = exp(-i/2 sum_k theta[k] P_k),
+ * the product of qdc_pauli_rot(theta[k], xmask, zmask[k]) in any order.  The strings must commute:
+ * every nY_k = popcount(xmask & zmask[k]) has one parity (a fermionic excitation under
+ * Jordan-Wigner, an XX + YY hopping term).  Each pair of amplitudes (i, i ^ xmask) is rotated by
+ * one angle, the diagonal layer's fixed-point phase on the pair's index: one sincos per pair.  A
+ * launch carries 128 terms (32 when it reduces gradients).  xmask == 0 forwards to the diagonal
+ * layer above, bit for bit.
+ * Errors: those of the diagonal layer ("pos is out of the bound." for xmask too) and "The
+ * strings of a layer must commute." (mixed parity of nY). */
+
+/* state <- U state */
+const char* qdc_pauli_xlayer(qdc_complex* state, unsigned long long xmask,
+                             const unsigned long long* zmask, const double* theta, size_t terms,
+                             size_t n);
+
+/* One reverse step, in one pass over both states: fwd <- U(-theta) fwd (uncompute), bwd <-
+ * U^T bwd (pull-back), dtheta[k] += dL/dtheta_k = 1/2 Im sum_i bwd[i] (P_k fwd)[i] for k < terms,
+ * fwd and bwd as the call receives them (qdc_pauli_rot_reverse's convention; one stream
+ * synchronisation for up to 1024 terms, one more per further 1024).
+ * bwd == NULL: uncompute only (dtheta must be NULL).  dtheta == NULL: constant layer.  The same
+ * call returns the same bits every time. */
+const char* qdc_pauli_xlayer_reverse(qdc_complex* fwd, qdc_complex* bwd, unsigned long long xmask,
+                                     const unsigned long long* zmask, const double* theta,
+                                     size_t terms, size_t n, double* dtheta);
+
+/* Host only, no GPU: out[0..5] = {L (log2 of the pair indices of a span: the diagonal layer's L,
+ * one less in the self-paired form), the deleted bit (the highest set bit of xmask; 0xffffffff
+ * where nothing is deleted from the masks' layout: xmask == 0, and the self-paired form, f32 at
+ * xmask == 1, which drops bit 0), low-mask groups of the reduced masks, forward launches, reverse
+ * launches without gradient, reverse launches with gradient}.  Returns the number of groups,
+ * SIZE_MAX on invalid arguments (non-commuting strings among them). */
+size_t qdc_pauli_xlayer_plan(unsigned long long xmask, const unsigned long long* zmask,
+                             size_t terms, size_t n, unsigned* out);
+
 #ifdef __cplusplus
 }
 #endif
