@@ -11,12 +11,14 @@
 
 #include "qdc/circuit.h"
 #include "qdc/dense.h"
+#include "qdc/overlap.h"
 #include "qdc/pauli.h"
 #include "qdc/sample.h"
 #include "qdc_device.hpp"
 #include "qdc_qk.hpp"
 #include "qdc_qkgrad.hpp"
 #include "qdc_pauli.hpp"
+#include "qdc_overlap.hpp"
 #include "qdc_paulirot.hpp"
 #include "qdc_paulilayer.hpp"
 #include "qdc_paulixlayer.hpp"
@@ -401,6 +403,57 @@ __attribute__((visibility("default"))) const char* qdc_pauli_inject(
   return qdc::pauli_inject(ctx, reinterpret_cast<const qdc::cx*>(fwd),
                            reinterpret_cast<qdc::cx*>(bwd), plan, (uint32_t)n, weight,
                            accumulate != 0);
+}
+
+// ---- overlaps and transition elements <a|H|b> (include/qdc/overlap.h, qdc_overlap.hpp) ---------
+
+__attribute__((visibility("default"))) const char* qdc_overlap(const qdc_complex* a,
+                                                               const qdc_complex* b, size_t n,
+                                                               double out[2]) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  return qdc::overlap(ctx, reinterpret_cast<const qdc::cx*>(a),
+                      reinterpret_cast<const qdc::cx*>(b), (uint32_t)n, out);
+}
+
+__attribute__((visibility("default"))) const char* qdc_pauli_overlap(
+    const qdc_complex* a, const qdc_complex* b, const unsigned long long* xmask,
+    const unsigned long long* zmask, const double* coeff, size_t terms, size_t n, double out[2]) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  qdc::PauliPlan plan;
+  QDC_TRY(qdc::pauli_plan(xmask, zmask, coeff, terms, n, plan));
+  return qdc::pauli_overlap(ctx, reinterpret_cast<const qdc::cx*>(a),
+                            reinterpret_cast<const qdc::cx*>(b), plan, (uint32_t)n, out);
+}
+
+__attribute__((visibility("default"))) const char* qdc_overlap_inject(
+    const qdc_complex* src, qdc_complex* bwd, size_t n, double g_re, double g_im,
+    int accumulate) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  if (!std::isfinite(g_re) || !std::isfinite(g_im))
+    return qdc::fail("Pauli coefficients must be finite.");
+  if (src == bwd) return qdc::fail("fwd and bwd must be different states.");
+  return qdc::overlap_inject(ctx, reinterpret_cast<const qdc::cx*>(src),
+                             reinterpret_cast<qdc::cx*>(bwd), (uint32_t)n, g_re, g_im,
+                             accumulate != 0);
+}
+
+__attribute__((visibility("default"))) const char* qdc_pauli_overlap_inject(
+    const qdc_complex* src, qdc_complex* bwd, const unsigned long long* xmask,
+    const unsigned long long* zmask, const double* coeff, size_t terms, size_t n, double g_re,
+    double g_im, int accumulate) {
+  QDC_ABI_BEGIN
+  QDC_TRY(qdc::check_n(n));
+  qdc::PauliPlan plan;
+  QDC_TRY(qdc::pauli_plan(xmask, zmask, coeff, terms, n, plan));
+  if (!std::isfinite(g_re) || !std::isfinite(g_im))
+    return qdc::fail("Pauli coefficients must be finite.");
+  if (src == bwd) return qdc::fail("fwd and bwd must be different states.");
+  return qdc::pauli_overlap_inject(ctx, reinterpret_cast<const qdc::cx*>(src),
+                                   reinterpret_cast<qdc::cx*>(bwd), plan, (uint32_t)n, g_re, g_im,
+                                   accumulate != 0);
 }
 
 // ---- Pauli rotations exp(-i theta/2 P) (include/qdc/pauli.h, qdc_paulirot.hpp) ----------------

@@ -12,6 +12,12 @@ one explicitly.  Input arrays must have the build's dtype (complex64 / complex12
 ``QuantizedTensor`` and the ``get_q*_grad`` / ``data_transfer`` helpers mirror
 ``src/quantized_tensor.rs:54-238`` over the 18-function C ABI, so the parity tests can follow
 the reference's own unit tests (``quantized_tensor.rs:400-609``).
+
+Beyond the reference, a ``QuantizedTensor`` reads ``pauli_energy``, ``norm_sq`` and ``sample``
+off one state, and ``overlap(other)`` = <self|other> and ``pauli_overlap(other, H)`` =
+<self|H|other> off two (``include/qdc/overlap.h``: complex, one pass over both states for the
+plain overlap); ``overlap_inject(src, bwd, g, obs)`` is their cotangent bwd += conj(g H src) for a
+complex upstream g = dL/dRe o + i dL/dIm o.
 """
 from __future__ import annotations
 
@@ -29,7 +35,7 @@ from .observable import (PauliSum, excitation, ladder_terms, layer_angles, layer
 
 __all__ = ["Circuit", "Circuit32", "Circuit64", "QuantizedTensor", "PanicException",
            "get_q1_grad", "get_q2_grad", "get_q2_grad_diag", "get_qk_grad", "data_transfer",
-           "PauliSum", "pauli_inject", "pauli_rot_reverse", "pauli_layer_reverse", "pauli_layer_plan",
+           "PauliSum", "pauli_inject", "overlap_inject", "pauli_rot_reverse", "pauli_layer_reverse", "pauli_layer_plan",
            "pauli_xlayer_reverse", "pauli_xlayer_plan", "xlayer_masks", "excitation", "ladder_terms",
            "sample_plan", "sample_assign", "circuit_class",
            "plan", "unpermute", "get_hadamard", "get_cnot"]
@@ -764,6 +770,30 @@ class QuantizedTensor:
         check(self._lib.qdc_pauli_energy(self._p, *obs._args(), self.qubits_number, C.byref(e)))
         return float(e.value)
 
+    def _same_shape(self, other):
+        if other.qubits_number != self.qubits_number:
+            raise PanicException("The two tensors have different sizes.")
+        if other._precision != self._precision:
+            raise PanicException("The two tensors have different precisions.")
+
+    def overlap(self, other: "QuantizedTensor") -> complex:
+        """<self|other> = sum_i conj(self[i]) other[i] (qdc_overlap, include/qdc/overlap.h): one
+        pass over both states, one host sync; neither state need be normalised."""
+        self._same_shape(other)
+        o = (C.c_double * 2)(0.0, 0.0)
+        check(self._lib.qdc_overlap(self._p, other._p, self.qubits_number, o))
+        return complex(o[0], o[1])
+
+    def pauli_overlap(self, other: "QuantizedTensor", obs: PauliSum) -> complex:
+        """<self|H|other> of a Pauli sum (qdc_pauli_overlap, include/qdc/overlap.h): the launches
+        of ``pauli_energy``, each over both states."""
+        self._same_shape(other)
+        if obs.qubits_number != self.qubits_number:
+            raise PanicException("The observable and the tensor have different sizes.")
+        o = (C.c_double * 2)(0.0, 0.0)
+        check(self._lib.qdc_pauli_overlap(self._p, other._p, *obs._args(), self.qubits_number, o))
+        return complex(o[0], o[1])
+
     def norm_sq(self) -> float:
         """N = sum_i |psi_i|^2 in double (qdc_sample with zero shots, include/qdc/sample.h): one
         pass over the state, one host sync."""
@@ -957,6 +987,23 @@ def pauli_inject(fwd, bwd, obs: PauliSum, weight=1.0, accumulate=True):
         raise PanicException("Pauli coefficients must be real.")
     check(fwd._lib.qdc_pauli_inject(fwd._p, bwd._p, *obs._args(), fwd.qubits_number, w.real,
                                     1 if accumulate else 0))
+
+
+def overlap_inject(src, bwd, g, obs: PauliSum | None = None, accumulate=True):
+    """The cotangent of a real loss L of o = <src|H|psi> (H = I when ``obs`` is None), src a
+    constant: bwd += conj(g H src) with g = dL/dRe o + i dL/dIm o (qdc_overlap_inject,
+    qdc_pauli_overlap_inject, include/qdc/overlap.h); ``accumulate=False`` overwrites bwd without
+    reading it.  |o|^2 has g = 2 o; src = psi and g = 2 w is ``pauli_inject(psi, bwd, obs, w)``."""
+    src._same_shape(bwd)
+    if obs is not None and obs.qubits_number != src.qubits_number:
+        raise PanicException("The observable and the tensor have different sizes.")
+    g = complex(g)
+    acc = 1 if accumulate else 0
+    if obs is None:
+        check(src._lib.qdc_overlap_inject(src._p, bwd._p, src.qubits_number, g.real, g.imag, acc))
+    else:
+        check(src._lib.qdc_pauli_overlap_inject(src._p, bwd._p, *obs._args(), src.qubits_number,
+                                                g.real, g.imag, acc))
 
 
 def _real_angle(theta) -> float:

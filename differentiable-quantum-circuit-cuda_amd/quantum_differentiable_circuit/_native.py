@@ -1,8 +1,9 @@
 """ctypes bindings of the HIP hot-path library (libqdc_f32.so / libqdc_f64.so).
 
 The C ABI is declared in ``include/qdc/primitives.h`` (the reference's 18 primitives,
-``src/primitives_bind.rs:15-119``), ``include/qdc/dense.h``, ``include/qdc/pauli.h`` and
-``include/qdc/sample.h`` (their extensions) and ``include/qdc/circuit.h`` (the circuit runtime that
+``src/primitives_bind.rs:15-119``), ``include/qdc/dense.h``, ``include/qdc/pauli.h``,
+``include/qdc/overlap.h`` and ``include/qdc/sample.h`` (their extensions) and
+``include/qdc/circuit.h`` (the circuit runtime that
 replaces ``src/circuit.rs`` / ``src/quantized_tensor.rs``).  There is no fallback: if the
 library is missing the import fails loudly, and every call that needs a GPU raises the HIP
 error the library reports.
@@ -44,6 +45,7 @@ RUNTIME = (
     "qdc_pauli_layer", "qdc_pauli_layer_reverse", "qdc_pauli_layer_plan",
     "qdc_pauli_xlayer", "qdc_pauli_xlayer_reverse", "qdc_pauli_xlayer_plan",
     "qdc_sample", "qdc_sample_plan", "qdc_sample_assign",
+    "qdc_overlap", "qdc_pauli_overlap", "qdc_overlap_inject", "qdc_pauli_overlap_inject",
 )
 
 
@@ -151,6 +153,13 @@ def _proto(lib):
         "qdc_sample_assign": (_E, [C.POINTER(C.c_double), _S, C.POINTER(C.c_double), _S,
                                    C.POINTER(C.c_ulonglong), C.POINTER(C.c_double),
                                    C.POINTER(C.c_ulonglong), C.POINTER(C.c_double)]),
+        "qdc_overlap": (_E, [_P, _P, _S, C.POINTER(C.c_double)]),
+        "qdc_pauli_overlap": (_E, [_P, _P, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong),
+                                   C.POINTER(C.c_double), _S, _S, C.POINTER(C.c_double)]),
+        "qdc_overlap_inject": (_E, [_P, _P, _S, C.c_double, C.c_double, C.c_int]),
+        "qdc_pauli_overlap_inject": (_E, [_P, _P, C.POINTER(C.c_ulonglong),
+                                          C.POINTER(C.c_ulonglong), C.POINTER(C.c_double), _S, _S,
+                                          C.c_double, C.c_double, C.c_int]),
         "qdc_abi_sync": (_E, []),
         "qdc_abi_profile": (_E, [C.c_int]),
         "qdc_abi_profile_collect": (_S, [C.POINTER(KernelStat), _S]),

@@ -43,6 +43,20 @@ Jordan-Wigner in one pass.
 its place among the outputs; ``forward`` and ``backward`` skip it.  An int seed gives the same
 sample on every ``run``, ``seed=None`` a fresh one.
 
+``get_overlap_op(target, obs=None)`` / ``get_overlap_op_with_grad`` read the transition element
+o = <target|H|psi> of the state at their place against a constant ``target`` (``obs=None``: H = I,
+the plain overlap; ``include/qdc/overlap.h``), a Python ``complex`` at its place among the outputs.
+``target`` is a ``QuantizedTensor`` of the circuit's size and precision, held by reference (the
+caller may refill it between calls), or a host vector, uploaded once when the op is added.  The
+differentiable op's cotangent in ``grads_wrt_density`` is the complex g = dL/dRe o + i dL/dIm o of
+a real loss L; backward is one ``overlap_inject(target, bwd, g, obs)``: bwd (+)= conj(g H target),
+into a newly allocated bwd when it is the first cotangent.  ``get_fidelity_op(target)`` /
+``get_fidelity_op_with_grad`` yield the float F = |<target|psi>|^2; the cotangent is a real weight
+w, and backward recomputes o on the uncomputed forward state (one overlap pass; nothing is cached
+from forward, as for an observable) and injects with g = 2 w o.  ``run`` yields both kinds of op,
+``forward`` only the differentiable ones.  The target is a constant: nothing is differentiated
+through it.
+
 Gates are 1-D arrays of 4^k values (2^k x 2^k row-major, local index bit (k-1-b) = qubit
 positions[b]); densities come back as (2^k, 2^k) arrays and gradients as 1-D arrays in forward
 order.  At k = 1, 2 every call lands on the q1 / q2 kernels, so a circuit of 1- and 2-qubit
@@ -61,14 +75,14 @@ from typing import List
 import numpy as np
 
 from . import (PanicException, PauliSum, QuantizedTensor, _real_angle, data_transfer, excitation,
-               get_qk_grad, layer_angles, layer_masks, pauli_inject, pauli_layer_reverse,
-               pauli_masks, pauli_rot_reverse, pauli_xlayer_reverse, xevolution_masks,
-               xlayer_masks)
+               get_qk_grad, layer_angles, layer_masks, overlap_inject, pauli_inject,
+               pauli_layer_reverse, pauli_masks, pauli_rot_reverse, pauli_xlayer_reverse,
+               xevolution_masks, xlayer_masks)
 from .abi_circuit import _slice
 
 (CONST_GATE, VAR_GATE, DENSITY, DIFF_DENSITY, OBSERVABLE, DIFF_OBSERVABLE, CONST_ROT,
  VAR_ROT, CONST_LAYER, VAR_LAYER, CONST_EVOL, VAR_EVOL, SAMPLE, CONST_XLAYER, VAR_XLAYER,
- CONST_XEVOL, VAR_XEVOL) = range(17)
+ CONST_XEVOL, VAR_XEVOL, OVERLAP, DIFF_OVERLAP, FIDELITY, DIFF_FIDELITY) = range(21)
 _CONST_KINDS = (CONST_GATE, CONST_ROT, CONST_LAYER, CONST_EVOL, CONST_XLAYER, CONST_XEVOL)
 _XLAYER_KINDS = (CONST_XLAYER, VAR_XLAYER, CONST_XEVOL, VAR_XEVOL)
 
@@ -112,6 +126,37 @@ class DenseCircuit:
 
     def get_observable_op(self, obs): self._push_observable(OBSERVABLE, obs)
     def get_observable_op_with_grad(self, obs): self._push_observable(DIFF_OBSERVABLE, obs)
+
+    def _push_overlap(self, kind, target, obs):
+        s = self.state
+        if isinstance(target, QuantizedTensor):  # held by reference: the caller may refill it
+            s._same_shape(target)
+        else:  # a host vector, uploaded once
+            v = np.asarray(target).reshape(-1)
+            if v.size != 1 << s.qubits_number:
+                raise PanicException("The two tensors have different sizes.")
+            target = QuantizedTensor.new_from_host(v, s._precision)
+        if obs is not None:
+            if not isinstance(obs, PauliSum):
+                raise TypeError("argument 'obs': expected a PauliSum")
+            if obs.qubits_number != s.qubits_number:
+                raise PanicException("The observable and the tensor have different sizes.")
+            if len(obs) == 0:
+                raise PanicException("The observable has no terms.")
+        self.instructions.append((kind, (target, obs)))
+
+    def get_overlap_op(self, target, obs=None): self._push_overlap(OVERLAP, target, obs)
+
+    def get_overlap_op_with_grad(self, target, obs=None):
+        self._push_overlap(DIFF_OVERLAP, target, obs)
+
+    def get_fidelity_op(self, target): self._push_overlap(FIDELITY, target, None)
+    def get_fidelity_op_with_grad(self, target): self._push_overlap(DIFF_FIDELITY, target, None)
+
+    @staticmethod
+    def _overlap(target, obs, s) -> complex:
+        """<target|H|s> (H = I when obs is None)."""
+        return target.overlap(s) if obs is None else target.pauli_overlap(s, obs)
 
     def _push_rotation(self, kind, ops):
         ops = ops if isinstance(ops, str) else tuple(ops)
@@ -233,6 +278,12 @@ class DenseCircuit:
             elif kind in (OBSERVABLE, DIFF_OBSERVABLE):
                 if kind == DIFF_OBSERVABLE or all_densities:
                     out.append(s.pauli_energy(pos))
+            elif kind in (OVERLAP, DIFF_OVERLAP):
+                if kind == DIFF_OVERLAP or all_densities:
+                    out.append(self._overlap(*pos, s))
+            elif kind in (FIDELITY, DIFF_FIDELITY):
+                if kind == DIFF_FIDELITY or all_densities:
+                    out.append(abs(self._overlap(*pos, s)) ** 2)
             elif kind == SAMPLE:
                 if all_densities:
                     shots, seed, qubits = pos
@@ -247,19 +298,21 @@ class DenseCircuit:
         return out
 
     def run(self, const_gates, var_gates):
-        """Every density matrix, every observable's energy and every sample, in instruction
-        order."""
+        """Every density matrix, every observable's energy, every overlap and fidelity and every
+        sample, in instruction order."""
         return self._forward(const_gates, var_gates, True)
 
     def forward(self, const_gates, var_gates):
-        """The differentiable density matrices and energies, in instruction order."""
+        """The differentiable density matrices, energies, overlaps and fidelities, in instruction
+        order."""
         return self._forward(const_gates, var_gates, False)
 
     # --- backward -------------------------------------------------------------------------
     def backward(self, grads_wrt_density, const_gates, var_gates) -> List[np.ndarray]:
         """Gradients of the variable gates, forward order; call after ``forward`` with the same
         gates.  ``grads_wrt_density`` holds, in the order of ``forward``'s outputs, a cotangent
-        matrix per differentiable density and a real weight per differentiable observable.
+        matrix per differentiable density, a real weight per differentiable observable or
+        fidelity and a complex g = dL/dRe o + i dL/dIm o per differentiable overlap.
         Leaves the forward state uncomputed back to the initial state."""
         if not self.instructions:
             raise PanicException("The circuit is empty.")
@@ -333,6 +386,20 @@ class DenseCircuit:
                     pauli_inject(fwd, bwd, pos, w.real, accumulate=False)
                 else:
                     pauli_inject(fwd, bwd, pos, w.real, accumulate=True)
+            elif kind in (DIFF_OVERLAP, DIFF_FIDELITY):
+                if not dens:
+                    raise PanicException(
+                        "The number of gradients wrt density matrices is less than required.")
+                g = complex(np.asarray(dens.pop()).reshape(()))
+                target, obs = pos
+                if kind == DIFF_FIDELITY:  # F = |o|^2: g = 2 w o, o recomputed on the uncomputed fwd
+                    if g.imag != 0.0:
+                        raise PanicException("Pauli coefficients must be real.")
+                    g = 2.0 * g.real * self._overlap(target, obs, fwd)
+                first = bwd is None
+                if first:
+                    bwd = QuantizedTensor(fwd.qubits_number, fwd._precision)
+                overlap_inject(target, bwd, g, obs, accumulate=not first)
         if cg:
             raise PanicException("Number of constant gates is more than required.")
         if vg:  # circuit.rs:426 words it this way
