@@ -460,8 +460,8 @@ QDC_API size_t qdc_fusion_schedule(size_t local_qubits, int backward, size_t fir
   if (inexact)
     for (size_t k = 0; k < n_instr; ++k) sens[k] = inexact[k] ? 1 : 0;
   qdc::FusionPlanner P{ins, sens, (uint32_t)local_qubits, true, true,
-                             max_ops > 0 ? (uint32_t)std::min(max_ops, qdc::FMAX_OPS)
-                                         : (uint32_t)qdc::FMAX_OPS,
+                             // (0: the 32 gates of the schedules its tests pin, not the bound)
+                             max_ops > 0 ? (uint32_t)std::min(max_ops, qdc::FMAX_OPS) : 32u,
                              lcmin > 0 ? (uint32_t)lcmin : 3u};
   using qdc::Knob;
   P.tile2_chunks = qdc::knob_uint(Knob::TILE2_CHUNKS, P.tile2_chunks);
@@ -470,6 +470,8 @@ QDC_API size_t qdc_fusion_schedule(size_t local_qubits, int backward, size_t fir
   P.permute = P.rq_grad = qdc::knob_int(Knob::SCHED_RQ, 0) != 0;
   P.permute = qdc::knob_int(Knob::SCHED_PERM, P.permute) != 0;  // f64: rq_grad only
   P.mirror = qdc::knob_int(Knob::SCHED_MIRROR, P.mirror) != 0;  // QDC_MIRROR's forward
+  // the Gamma cap of the schedules its tests pin unless asked for (the runtime's: QDC_RQ_GCAP)
+  P.gamma_cap = (uint32_t)qdc::knob_int(Knob::SCHED_GCAP, 16, 1, qdc::FMAX_GRAD_RQ);
   P.defer_q1 = qdc::knob_int(Knob::DEFER_Q1, P.defer_q1) != 0;
   P.search = qdc::knob_int(Knob::FUSE_SEARCH, P.search) != 0;
   P.perm_low = qdc::knob_uint(Knob::RQ_PERM_LOW, P.perm_low);

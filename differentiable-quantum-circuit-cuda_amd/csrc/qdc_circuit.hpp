@@ -219,7 +219,8 @@ struct Circuit {
   struct Knobs {
     // fused multi-gate passes
     int fuse = 1;             // 0: one HBM pass per gate
-    uint32_t fuse_max_ops = FMAX_OPS;
+    // gates per fused pass: twice the Gamma cap (a brickwork stage holds two gates and more)
+    uint32_t fuse_max_ops = 2 * RQ_GCAP_DEFAULT;
     uint32_t fuse_lcmin = 3;  // min contiguous chunk bits of a fused tile (128-B rows)
     int fuse_meas = 1;        // densities / cotangent injections join fused passes
     int use_rq = 1;           // f32 gate passes run register-resident (qdc_rq.hpp)
@@ -249,7 +250,10 @@ struct Circuit {
     int spec_async = sizeof(real) == 4 ? 1 : 0;
     int rq_permute = 1;      // gate-only passes permute their tile's qubits (QDC_RQ_PERM)
     int rq_perm_shard = 1;    // ... on sharded circuits too (QDC_RQ_PERM_SHARD)
-    int rq_grad32 = 1;        // two-state passes hold up to FMAX_GRAD_RQ Gamma stages (QDC_RQ_GRAD32)
+    int rq_grad32 = 1;        // two-state passes hold up to rq_gcap Gamma stages (QDC_RQ_GRAD32)
+    // Gamma stages a two-state register-resident pass holds (QDC_RQ_GCAP, 1 .. FMAX_GRAD_RQ;
+    // FusionPlanner::gamma_cap).  The defaults were measured: DESIGN.md "Fewer, fuller passes"
+    uint32_t rq_gcap = RQ_GCAP_DEFAULT;
     int rq_maxcl = 1;         // relayouts chosen by max closure, else greedily (QDC_RQ_MAXCL)
     uint32_t rq_perm_low = 0;  // low positions a permuting pass fills, 0: default (QDC_RQ_PERM_LOW)
     int rq_gstage = 1;  // two-state passes capped by Gamma stages, not variable gates (QDC_RQ_GSTAGE)
@@ -315,6 +319,7 @@ struct Circuit {
       f(Knob::RQ_PERM_SHARD, k.rq_perm_shard);
       f(Knob::RQ_PERM_LOW, k.rq_perm_low);
       f(Knob::RQ_GRAD32, k.rq_grad32);
+      f(Knob::RQ_GCAP, k.rq_gcap, 1, FMAX_GRAD_RQ);
       f(Knob::RQ_MAXCL, k.rq_maxcl);
       f(Knob::RQ_GSTAGE, k.rq_gstage);
       f(Knob::TILE1_CHUNKS, k.tile1_chunks);
@@ -946,6 +951,7 @@ struct Circuit {
     P.permute = k.rq_permute && k.use_rq && (g == 0 || k.rq_perm_shard) && sizeof(real) == 4;
     P.ng = g;
     P.rq_grad = k.rq_grad32 && k.use_rq && (sizeof(real) == 4 || k.rq64);
+    P.gamma_cap = k.rq_gcap;
     if (k.rq_perm_low) P.perm_low = k.rq_perm_low;
     P.tile1_chunks = k.tile1_chunks;
     P.mirror = mirror_on() && mirror_fwd;
@@ -1334,6 +1340,7 @@ struct Circuit {
     // the kernels index their per-wave accumulators by reduction op: a pass with more
     // reduction ops than accumulators is a planner bug, never folded into another slot
     const size_t nred = it.grad_slots.size();
+    // (the kernels' storage bound; the planner's cap, k.rq_gcap, lies within it)
     const size_t cap = rq ? (size_t)FMAX_GRAD_RQ : (size_t)FMAX_GRAD;
     if (nred > cap)
       return fail("internal: a fused pass has %zu reduction ops, the kernel holds %zu", nred, cap);
@@ -1606,14 +1613,16 @@ struct Circuit {
     // partials) and the one-state kernels (no reduction code) rest on that.
     if (!two && fg.ngrad > 0)
       return fail("internal: a one-state register-resident pass with %u reductions", fg.ngrad);
-    QDC_TRY(fused_grid((const void*)V->kernel, spec && V->own_grid ? spec : nullptr, (int)V->threads,
+    // (a pass of more than RQ_GACC_SMALL Gamma stages: the instance with FMAX_GRAD_RQ accumulators)
+    const rq_kernel_t kernel = V->kernel_for(fg.ngrad);
+    QDC_TRY(fused_grid((const void*)kernel, spec && V->own_grid ? spec : nullptr, (int)V->threads,
                        use.grid));
     fgeo g = fg;
     QDC_TRY(size_grid(ctx, g, use, V->dyn, "fused"));
     if (spec)
       return ctx.launch_module(name, bytes, spec, use.grid, V->threads, f, b, fops, mats, g, l0,
                                partials, stride);
-    return ctx.launch_block(name, bytes, V->kernel, use.grid, V->threads, f, b, fops, mats, g, l0,
+    return ctx.launch_block(name, bytes, kernel, use.grid, V->threads, f, b, fops, mats, g, l0,
                             partials, stride);
   }
   // One wave of resident blocks of a kernel (occupancy query, cached per kernel), or

@@ -70,6 +70,13 @@ struct FusionItem {
   std::vector<std::pair<uint32_t, uint32_t>> swaps;
 };
 
+// Gamma stages a two-state register-resident pass holds by default (Circuit::Knobs::rq_gcap,
+// QDC_RQ_GCAP; at most FMAX_GRAD_RQ).  DESIGN.md "Fewer, fuller passes" has the measurements
+// behind both values.
+constexpr uint32_t RQ_GCAP_DEFAULT = sizeof(real) == 4 ? 32u : 16u;
+static_assert(RQ_GCAP_DEFAULT <= (uint32_t)FMAX_GRAD_RQ && 2 * RQ_GCAP_DEFAULT <= (uint32_t)FMAX_OPS,
+              "the default caps lie within the storage bounds");
+
 struct FusionPlanner {
   static constexpr uint32_t TILE_CHUNKS_1 = 2048;  // one-state fused tile (chunks)
   static constexpr uint32_t TILE_CHUNKS_2 = 1024;  // two-state fused tile (chunks per state)
@@ -87,8 +94,11 @@ struct FusionPlanner {
   // physical positions 0..LV+2 that every tile holds, so later tiles are not spent on pinned
   // qubits no op of theirs needs.
   bool permute = false;
-  // two-state gate passes run register-resident (k_rq: FMAX_GRAD_RQ Gamma accumulators)
+  // two-state gate passes run register-resident and hold up to gamma_cap Gamma stages
   bool rq_grad = false;
+  // ... that many (<= FMAX_GRAD_RQ, the kernels' accumulators): QDC_RQ_GCAP in the runtime,
+  // QDC_SCHED_GCAP in the qdc_fusion_schedule hook
+  uint32_t gamma_cap = RQ_GCAP_DEFAULT;
   // ... and are capped by their Gamma STAGES (stages holding a variable gate: one accumulator
   // each), not by their variable gates: a brickwork stage holds up to three of them
   bool gamma_stage_cap = true;
@@ -340,7 +350,7 @@ struct FusionPlanner {
       const bool two = (backward && i >= first_inject) || mfwd;
       const bool gstage = two && rq_grad && gamma_stage_cap;
       const uint32_t gmax = gstage ? fuse_max_ops
-                            : (two && rq_grad) ? (uint32_t)FMAX_GRAD_RQ : (uint32_t)FMAX_GRAD;
+                            : (two && rq_grad) ? gamma_cap : (uint32_t)FMAX_GRAD;
       const PassRules rules{backward, mfwd, two, gstage, gmax, T};
       std::vector<uint32_t> rem;
       for (size_t k = i; k < j; ++k) rem.push_back((uint32_t)k);
@@ -430,9 +440,9 @@ struct FusionPlanner {
     }
     // Gamma-stage cap: drop gates from the end of the pass (in pass order no kept gate
     // depends on a dropped one) until its Gamma stages fit the accumulators
-    if (r.gstage && nred > (uint32_t)FMAX_GRAD_RQ) {
+    if (r.gstage && nred > gamma_cap) {
       bool cut = false;
-      while (pass.size() > 1 && gamma_stages(pass, plan, !mfwd) > (uint32_t)FMAX_GRAD_RQ) {
+      while (pass.size() > 1 && gamma_stages(pass, plan, !mfwd) > gamma_cap) {
         rest.push_back(pass.back());
         pass.pop_back();
         cut = true;
@@ -485,7 +495,7 @@ struct FusionPlanner {
       return (uint32_t)stage_partition(p.ops, plan, r.backward).size();
     };
     auto at_cap = [&](const ScannedPass& p, uint32_t st) {
-      return p.ops.size() >= fuse_max_ops || (r.gstage && st >= (uint32_t)FMAX_GRAD_RQ) ||
+      return p.ops.size() >= fuse_max_ops || (r.gstage && st >= gamma_cap) ||
              p.rest.empty();
     };
     auto width = [&](const ScannedPass& p) {

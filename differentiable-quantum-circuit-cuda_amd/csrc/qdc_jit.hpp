@@ -81,18 +81,32 @@ struct SpecKind {
   uint32_t tb, ns;     // thread bits and register slots of a tile (registers per state 2^ns)
   bool bar;            // several waves per tile: block barriers around relayouts
   const char* prefix;  // kernel name prefix (the bench's kernel classes key on it)
-  const char* pass;    // the generic kernel's body with the program
+  std::string pass;    // the generic kernel's body with the program
   uint32_t threads;
   const char* waves;   // amdgpu_waves_per_eu of the generic kernel
   bool half = false;   // relayouts through half the buffer (spec_xchg_half)
 };
 // The specialized pass of a variant (qdc_variant.hpp; V.prefix != nullptr), or its half-buffer
 // form (V.pass_half != nullptr): every relayout in two rounds through half the buffer.
-inline SpecKind spec_kind(const RqVariant& V, bool half = false) {
+// gamma: the program's Gamma stages.  More than RQ_GACC_SMALL: the pass body is instantiated
+// with FMAX_GRAD_RQ accumulators (rw_pass's GA, after HALF); up to it, the source is the one
+// written for the smaller storage bound, character for character.
+inline SpecKind spec_kind(const RqVariant& V, bool half = false, uint32_t gamma = 0) {
   uint32_t tb = 0;
   while ((1u << tb) < V.threads) ++tb;
-  return {V.two, tb, V.ns, V.threads > 64, V.prefix, half ? V.pass_half : V.pass, V.threads,
+  std::string pass = half ? V.pass_half : V.pass;
+  if (V.two && gamma > (uint32_t)RQ_GACC_SMALL) {
+    pass.pop_back();  // the closing '>'
+    pass += std::string(half ? "" : ", false") + ", " + std::to_string((int)FMAX_GRAD_RQ) + ">";
+  }
+  return {V.two, tb, V.ns, V.threads > 64, V.prefix, pass, V.threads,
           half ? V.waves_half : V.waves, half};
+}
+// the Gamma stages of a pass program
+inline uint32_t spec_gamma_stages(const std::vector<SpecStep>& steps) {
+  uint32_t n = 0;
+  for (const SpecStep& s : steps) n += (!s.relayout && (s.F.kind & FOP_GAMMA)) ? 1u : 0u;
+  return n;
 }
 // The register slot a relayout keeps (the same tile bit in the same slot of both layouts), or
 // -1: a half-buffer relayout splits on it (spec_xchg_half).
@@ -334,7 +348,7 @@ inline uint64_t spec_fingerprint(const std::string& defines, const std::string& 
 // kernel name: prefix + hash of the build fingerprint, the generic kernel and the program
 inline std::string spec_kernel_name_fp(const std::string& body, const SpecKind& K, uint64_t fp) {
   char nm[48];
-  uint64_t h = spec_hash(std::string(K.pass) + "\n" + body);
+  uint64_t h = spec_hash(K.pass + "\n" + body);
   h = fnv_more(h, &fp, sizeof fp);
   snprintf(nm, sizeof nm, "%s%016llx", K.prefix, (unsigned long long)h);
   return nm;

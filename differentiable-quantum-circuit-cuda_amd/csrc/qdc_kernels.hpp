@@ -1066,18 +1066,24 @@ __global__ __launch_bounds__(BLOCK) void k_finalize(const cx* __restrict__ parti
 // wave's accumulator slot; one partial per block and gradient stage at the end.
 // ---------------------------------------------------------------------------------------
 #ifndef QDC_FMAX_OPS
-#define QDC_FMAX_OPS 32
+#define QDC_FMAX_OPS 64
 #endif
 constexpr int FMAX_OPS = QDC_FMAX_OPS;   // gates per fused pass (>= its stages)
 constexpr int FMAX_GRAD = 16;  // gradient gates per fused pass (>= its gradient stages)
 #ifndef QDC_FMAX_GRAD_RQ
-#define QDC_FMAX_GRAD_RQ 16
+#define QDC_FMAX_GRAD_RQ 32
 #endif
-// the same for register-resident two-state passes (per-wave LDS accumulators).  Measured at
-// C2 n=28: 24 / 32 give 20 % / 15 % fewer reverse passes, each 33 % / 23 % slower (more
-// relayouts per stage, 7 / 6 blocks per CU): 16 is best.
+// The same for register-resident two-state passes: the bound of the storage (per-wave LDS
+// accumulators, partial slots).  The cap a circuit plans with is a value (QDC_RQ_GCAP,
+// FusionPlanner::gamma_cap) within it.  A pass of at most RQ_GACC_SMALL Gamma stages runs on the
+// kernels instantiated with RQ_GACC_SMALL accumulators (2 KiB of LDS per wave in f32, 4 KiB in
+// f64), a fuller one on those with FMAX_GRAD_RQ (twice that), so the passes that fit the
+// smaller footprint keep it: DESIGN.md "Fewer, fuller passes" has the resource table and what
+// the cap measured.
 constexpr int FMAX_GRAD_RQ = QDC_FMAX_GRAD_RQ;
+constexpr int RQ_GACC_SMALL = FMAX_GRAD_RQ < 16 ? FMAX_GRAD_RQ : 16;
 static_assert(FMAX_GRAD_RQ >= 1 && FMAX_GRAD >= 1, "at least one reduction accumulator");
+static_assert(FMAX_GRAD_RQ <= FIN_MAX, "a pass's partial slots are pending together (Ctx::flush)");
 static_assert(FMAX_OPS <= 64, "rq_plan keeps stage sets in 64-bit masks");
 constexpr int FMAX_ROWS = 8;   // far qubits per tile
 constexpr int FACC = 32;       // reals per gradient accumulator (16 complex)

@@ -67,7 +67,7 @@ enum class KnobScope { Process, Context, Circuit, Call, Hook };
     "units in flight per wave of LANE launches, \"u0,u1,u2\" per op class as QDC_LANE")            \
   /* ---- Circuit::Knobs (qdc_circuit.hpp) ---- */                                                 \
   X(FUSE, Circuit, "1", "0: one HBM pass per gate (single-gate kernels only)")                     \
-  X(FUSE_MAX_OPS, Circuit, "32", "gates per fused pass (1 .. FMAX_OPS)")                           \
+  X(FUSE_MAX_OPS, Circuit, "f32: 64, f64: 32", "gates per fused pass (1 .. FMAX_OPS)")             \
   X(FUSE_MEAS, Circuit, "1", "0: densities / cotangent injections stay single passes")             \
   X(FUSE_LCMIN, Circuit, "3", "minimum contiguous chunk bits of a fused tile (1 .. 6)")            \
   X(FUSED_BLOCKS, Circuit, "0",                                                                    \
@@ -85,7 +85,9 @@ enum class KnobScope { Process, Context, Circuit, Call, Hook };
   X(RQ_PERM_SHARD, Circuit, "1", "0: no permuting passes on sharded circuits")                     \
   X(RQ_PERM_LOW, Circuit, "0", "low positions a permuting pass fills; 0: the planner's default")   \
   X(RQ_GRAD32, Circuit, "1",                                                                       \
-    "0: two-state passes hold FMAX_GRAD instead of FMAX_GRAD_RQ Gamma stages")                     \
+    "0: two-state passes hold FMAX_GRAD instead of QDC_RQ_GCAP Gamma stages")                      \
+  X(RQ_GCAP, Circuit, "f32: 32, f64: 16",                                                          \
+    "Gamma stages a two-state register-resident pass holds (1 .. FMAX_GRAD_RQ)")                   \
   X(RQ_MAXCL, Circuit, "1", "0: relayouts chosen greedily instead of by max closure")              \
   X(RQ_GSTAGE, Circuit, "1",                                                                       \
     "0: two-state passes capped by variable gates instead of Gamma stages")                        \
@@ -146,6 +148,8 @@ enum class KnobScope { Process, Context, Circuit, Call, Hook };
     "qdc_fusion_schedule: permuting passes and the register-resident Gamma cap")                   \
   X(SCHED_PERM, Hook, "as QDC_SCHED_RQ", "qdc_fusion_schedule: permuting passes alone")            \
   X(SCHED_MIRROR, Hook, "0", "qdc_fusion_schedule: the mirrored forward schedule")                 \
+  X(SCHED_GCAP, Hook, "16",                                                                        \
+    "qdc_fusion_schedule: Gamma stages of a two-state pass (1 .. FMAX_GRAD_RQ)")                   \
   X(TILE2_CHUNKS, Hook, "1024", "qdc_fusion_schedule: two-state fused tile in chunks")             \
   X(RQ_KEEP, Hook, "0", "qdc_rq_plan: every relayout keeps a register slot (half buffers)")        \
   X(PRECOMPILE_DUMP, Hook, "unset",                                                                \

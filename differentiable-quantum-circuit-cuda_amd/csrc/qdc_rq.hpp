@@ -475,7 +475,8 @@ struct SpecEnv {
   uint32_t t;          // the block's thread
   char* bufb;          // the relayout buffer
 };
-template <bool TWO, int NT, bool PF, class PROG = void>
+// GA: Gamma accumulators (two-state: the pass's Gamma stages are at most GA)
+template <bool TWO, int NT, bool PF, class PROG = void, int GA = RQ_GACC_SMALL>
 __device__ __forceinline__ void rq_pass(chunk* __restrict__ f, chunk* __restrict__ b,
                                         const fop* __restrict__ ops, const cx* __restrict__ mats,
                                         fgeo fg, uint32_t l0, cx* __restrict__ partials,
@@ -484,11 +485,11 @@ __device__ __forceinline__ void rq_pass(chunk* __restrict__ f, chunk* __restrict
   constexpr int CPT = RQ_R / VEC;  // chunks of each state per thread (8)
   constexpr int TA = NT * RQ_R;    // amplitudes per tile and state
   __shared__ cx buf[TA];
-  __shared__ real accw[TWO ? NT / 64 : 1][TWO ? FMAX_GRAD_RQ : 1][FACC];
+  __shared__ real accw[TWO ? NT / 64 : 1][TWO ? GA : 1][FACC];
   const uint32_t t = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane((int)(t >> 6));
   if constexpr (TWO) {
-    for (uint32_t i = t; i < (NT / 64) * FMAX_GRAD_RQ * FACC; i += NT) (&accw[0][0][0])[i] = 0;
+    for (uint32_t i = t; i < (NT / 64) * GA * FACC; i += NT) (&accw[0][0][0])[i] = 0;
     // a wave's accumulators are zeroed partly by other waves; a Gamma stage can come before
     // the pass's first relayout barrier
     __syncthreads();
@@ -584,7 +585,8 @@ __device__ __forceinline__ void rq_pass(chunk* __restrict__ f, chunk* __restrict
       const uint32_t kind = op.kind & 7u;
       const bool gamma = TWO && (op.kind & FOP_GAMMA) && !(QDC_RQ_ABL & 4);
       const cx* M = mats + op.mat;
-      // ri < FMAX_GRAD_RQ: classify_pass rejects a pass with more Gamma stages
+      // ri < GA: classify_pass rejects a pass with more Gamma stages than FMAX_GRAD_RQ, and
+      // launch_rq runs one with more than RQ_GACC_SMALL on the GA = FMAX_GRAD_RQ instance
       real* acc = TWO ? &accw[wave][ri][0] : nullptr;
       if ((QDC_RQ_ABL & 2) && kind == FK_RELAYOUT) {
         lcur = op.mat;
@@ -715,7 +717,7 @@ __device__ __forceinline__ void rq_pass(chunk* __restrict__ f, chunk* __restrict
     }
   }
 }
-template <bool TWO, int NT, bool PF>
+template <bool TWO, int NT, bool PF, int GA = RQ_GACC_SMALL>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(PF ? QDC_RQ_PF_WAVES : 4)))
 void k_rq(chunk* __restrict__ f, chunk* __restrict__ b, const fop* __restrict__ ops,
           const cx* __restrict__ mats, fgeo fg, uint32_t l0, cx* __restrict__ partials,
@@ -723,7 +725,8 @@ void k_rq(chunk* __restrict__ f, chunk* __restrict__ b, const fop* __restrict__ 
   // the instances the runtime launches (the rows of qdc_variant.hpp): two-state 2^11 tiles
   // without prefetch, one-state 2^11 / 2^12 tiles with and without
   static_assert(TWO ? (NT == 128 && !PF) : (NT == 128 || NT == 256), "k_rq: not a launched variant");
-  rq_pass<TWO, NT, PF>(f, b, ops, mats, fg, l0, partials, slot_stride);
+  static_assert(TWO || GA == RQ_GACC_SMALL, "one-state passes hold no accumulators");
+  rq_pass<TWO, NT, PF, void, GA>(f, b, ops, mats, fg, l0, partials, slot_stride);
 }
 
 // One wave per tile (k_rw): the same programs, layouts and HBM addressing as k_rq with NT
@@ -757,7 +760,9 @@ void k_rq(chunk* __restrict__ f, chunk* __restrict__ b, const fop* __restrict__ 
 // block-wide.
 // PROG (not void; not the two-state prefetching instance): the pass program as straight-line stage calls
 // (qdc_spec.hpp) in place of the interpreted op loop.
-template <bool TWO, int NE, bool PF, int W, bool S5 = false, class PROG = void, bool HALF = false>
+// GA: Gamma accumulators (two-state: the pass's Gamma stages are at most GA).
+template <bool TWO, int NE, bool PF, int W, bool S5 = false, class PROG = void, bool HALF = false,
+          int GA = RQ_GACC_SMALL>
 __device__ __forceinline__ void rw_pass(chunk* __restrict__ f, chunk* __restrict__ b,
                                         const fop* __restrict__ ops, const cx* __restrict__ mats,
                                         fgeo fg, uint32_t l0, cx* __restrict__ partials,
@@ -775,10 +780,10 @@ __device__ __forceinline__ void rw_pass(chunk* __restrict__ f, chunk* __restrict
   // the buffer, qdc_spec.hpp spec_xchg_half)
   static_assert(!HALF || (W == 1 && !std::is_void<PROG>::value), "half buffers: one-wave programs");
   __shared__ cx buf[64 * W * R / (HALF ? 2 : 1)];
-  __shared__ real accw[TWO ? FMAX_GRAD_RQ : 1][FACC];
+  __shared__ real accw[TWO ? GA : 1][FACC];
   const uint32_t lane = threadIdx.x;  // the block's thread (W = 1: the lane)
   if constexpr (TWO) {
-    for (uint32_t i = lane; i < FMAX_GRAD_RQ * FACC; i += 64) (&accw[0][0])[i] = 0;
+    for (uint32_t i = lane; i < GA * FACC; i += 64) (&accw[0][0])[i] = 0;
   }
   const rqio* io = reinterpret_cast<const rqio*>(mats + l0 + sizeof(rq_layout) / sizeof(cx));
   uint64_t thr_ld = 0, thr_st = 0;  // this lane's chunk offsets in the load / store layout
@@ -1136,7 +1141,7 @@ __device__ __forceinline__ void rw_pass(chunk* __restrict__ f, chunk* __restrict
     }
   }
 }
-template <bool TWO, int NE, bool PF, int W, bool S5 = false>
+template <bool TWO, int NE, bool PF, int W, bool S5 = false, int GA = RQ_GACC_SMALL>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(
     (PF && TWO) ? 1 : (!TWO && !PF) ? QDC_RW_WAVES_ONE : QDC_RW_WAVES,
     (PF && TWO) ? 1 : (!TWO && !PF) ? QDC_RW_WAVES_ONE : QDC_RW_WAVES)))
@@ -1151,7 +1156,8 @@ void k_rw(chunk* __restrict__ f, chunk* __restrict__ b, const fop* __restrict__ 
                                             : (W == 1 ? (!PF || S5) : (W == 2 && !PF && !S5))))
                         : (NE == 1 && VEC == 1 && !PF && !S5 && (W == 1 || (W == 2 && !TWO))),
                 "k_rw: not a launched variant");
-  rw_pass<TWO, NE, PF, W, S5>(f, b, ops, mats, fg, l0, partials, slot_stride);
+  static_assert(TWO || GA == RQ_GACC_SMALL, "one-state passes hold no accumulators");
+  rw_pass<TWO, NE, PF, W, S5, void, false, GA>(f, b, ops, mats, fg, l0, partials, slot_stride);
 }
 
 }  // namespace qdc

@@ -131,7 +131,7 @@ inline bool spec_half_buffer(const RqVariant& V, bool spec_half, const std::vect
 // The specialized kernel (name, source) of the pass program `steps` on variant V
 inline SpecEntry spec_kernel_of(const std::vector<SpecStep>& steps, const RqVariant& V,
                                 uint32_t tbits, bool half) {
-  const SpecKind K = spec_kind(V, half);
+  const SpecKind K = spec_kind(V, half, spec_gamma_stages(steps));
   const std::string body = spec_program_source(steps, tbits, K);
   SpecEntry e;
   e.name = spec_kernel_name(body, K);

@@ -36,6 +36,15 @@ struct RqVariant {
   // a specialized launch sizes its grid from the specialized kernel's own occupancy (else from
   // the generic kernel's).  Kept exactly as measured; DESIGN.md lists unifying it as follow-up
   bool own_grid;
+  // two-state rows: the generic kernel with FMAX_GRAD_RQ Gamma accumulators, which runs the
+  // passes of more than RQ_GACC_SMALL Gamma stages (`kernel` holds RQ_GACC_SMALL: the LDS
+  // footprint of a pass that needs no more does not grow with the storage bound); nullptr: a
+  // one-state row
+  rq_kernel_t kernel_wide = nullptr;
+  // the generic kernel of a pass with `gamma` Gamma stages
+  rq_kernel_t kernel_for(uint32_t gamma) const {
+    return gamma > (uint32_t)RQ_GACC_SMALL && kernel_wide ? kernel_wide : kernel;
+  }
 };
 
 #define QDC_RQ_KERNEL(...) #__VA_ARGS__, __VA_ARGS__
@@ -52,11 +61,15 @@ inline const RqVariant* rq_variants() {
   static const RqVariant V[RV_COUNT] = {
       {QDC_RQ_KERNEL(k_rw<true, 2, false, 1, true>), true, 11, 64, 5, true, "qdc_spec_",
        "qdc::rw_pass<true, 2, false, 1, true, Prog>", "QDC_RW_WAVES, QDC_RW_WAVES",
-       "qdc::rw_pass<true, 2, false, 1, true, Prog, true>", "QDC_RW_WAVES, QDC_RW_WAVES", true},
-      {QDC_RQ_KERNEL(k_rw<true, 2, false, 1>), true, 11, 64, 4, true, QDC_RQ_NO_SPEC},
+       "qdc::rw_pass<true, 2, false, 1, true, Prog, true>", "QDC_RW_WAVES, QDC_RW_WAVES", true,
+       k_rw<true, 2, false, 1, true, FMAX_GRAD_RQ>},
+      {QDC_RQ_KERNEL(k_rw<true, 2, false, 1>), true, 11, 64, 4, true, QDC_RQ_NO_SPEC,
+       k_rw<true, 2, false, 1, false, FMAX_GRAD_RQ>},
       // the next tile prefetched into AGPRs, one wave per SIMD
-      {QDC_RQ_KERNEL(k_rw<true, 2, true, 1>), true, 11, 64, 4, false, QDC_RQ_NO_SPEC},
-      {QDC_RQ_KERNEL(k_rq<true, 128, false>), true, 11, 128, 4, false, QDC_RQ_NO_SPEC},
+      {QDC_RQ_KERNEL(k_rw<true, 2, true, 1>), true, 11, 64, 4, false, QDC_RQ_NO_SPEC,
+       k_rw<true, 2, true, 1, false, FMAX_GRAD_RQ>},
+      {QDC_RQ_KERNEL(k_rq<true, 128, false>), true, 11, 128, 4, false, QDC_RQ_NO_SPEC,
+       k_rq<true, 128, false, FMAX_GRAD_RQ>},
       // one wave per 2^11 tile (QDC_TILE1_CHUNKS=1024, or a mirrored forward).  The half-buffer
       // form needs 8 KiB of LDS per wave and is compiled for QDC_RW_WAVES_HALF_ONE [5] waves per
       // SIMD (~96 VGPRs, a few spilled; 4 waves at 106 VGPRs measured 0.7-1.0 % slower per step)
@@ -87,7 +100,7 @@ inline const RqVariant* rq_variants() {
   static const RqVariant V[RV_COUNT] = {
       {QDC_RQ_KERNEL(k_rw<true, 1, false, 1>), true, 10, 64, 4, true, "qdc_spec_d_",
        "qdc::rw_pass<true, 1, false, 1, false, Prog>", "QDC_RW_WAVES, QDC_RW_WAVES", nullptr, nullptr,
-       false},
+       false, k_rw<true, 1, false, 1, false, FMAX_GRAD_RQ>},
       {QDC_RQ_KERNEL(k_rw<false, 1, false, 1>), false, 10, 64, 4, true, "qdc_specf_d_",
        "qdc::rw_pass<false, 1, false, 1, false, Prog>", "QDC_RW_WAVES_ONE, QDC_RW_WAVES_ONE", nullptr,
        nullptr, false},
